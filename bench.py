@@ -9,11 +9,15 @@ Workload = BASELINE configs[1] ("C2"): 32 tiles x 100k points, 64^3 grid, 16 GEN
 Multi-GPU: one process per GPU (torchrun), tiles sharded per rank, NO data-path collective; the barrier and the
 max-over-ranks of the timed region are the only collectives (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (K3) with its duration measured live with
-HIP events on the launch stream; `cpu_baseline` is the oracle (CPU restatement of the reference path, the only
-place this file touches oracle/) timed on the host cores on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up (W steps, the clock spin-up, W steps), times the K steps
+and reports the headline (`value`, `ms_per_step`).  `--full` adds everything else, each from runs of its own: the
+cold and fp32 figures, the extras, the sustained loop and `cpu_baseline`, and the stage events inside the timed loop
+that `roofline` rests on (the dominant kernel's duration measured live with HIP events on the launch stream).
+`cpu_baseline` is the oracle (CPU restatement of the reference path, the only place this file touches oracle/)
+timed on the host cores on a bounded sample.  `--dump-outputs DIR` writes rank 0's output of the last timed step
+(see dump_outputs); the inputs depend on the arguments alone.
 """
 import argparse
 import gc
@@ -56,14 +60,19 @@ def parse():
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--spinup-ms", type=float, default=200.0,
                     help="untimed spin-up of the same step before the warm-up steps (device clocks settle)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (cold / fp32 / sustained figures, roofline, "
+                         "extras, CPU baseline); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     ap.add_argument("--event-every", type=int, default=0,
-                    help="record the HIP events that time the stages on every N-th timed step; 0 (default) = "
+                    help="(--full) record the HIP events that time the stages on every N-th timed step; 0 (default) = "
                          "max(5, steps / 8) (1 below 8 steps): at least four timed launches at the default 20 steps, "
                          "eight at 64 and more.  [measured] a record costs ~2.5 us of GPU time plus host work next to "
                          "a queue that is barely ahead: 187.3 / 159.1 us per step with the records on every 4th / "
                          "every 50th of 200 steps")
     ap.add_argument("--sustain-ms", type=float, default=6000.0,
-                    help="also time the same eager step back to back over at least this much wall time "
+                    help="(--full) also time the same eager step back to back over at least this much wall time "
                          "(`value_sustained`; 0 = skip).  6 s by default: an external sampler with a ~5 s period (the "
                          "driver's gpu_busy probe, rocm-smi) then has at least one sample inside the loop; the loop also "
                          "samples the device's own gpu_busy_percent (sysfs) every 100 ms and reports what it saw")
@@ -72,8 +81,12 @@ def parse():
                     help="N>1 code path on a one-GPU box: every rank uses cuda:0, process group over gloo (not a "
                          "measurement)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the graph-replay and skip-empty extras (profiling runs: keeps per-kernel averages clean)")
-    return ap.parse_args()
+                    help="(--full) skip the graph-replay and skip-empty extras (profiling runs: keeps per-kernel averages "
+                         "clean)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_if_needed(args):
@@ -252,6 +265,24 @@ def reference_defaults_extra(sna, dev, ev, spin, args, B=64):
     return out
 
 
+DUMP_WHOLE_MAX = 1 << 23    # values per array written whole (32 MiB of fp32: C2's head output exactly)
+DUMP_SAMPLE = 1 << 20       # values kept of a larger array
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32 (float64 stays float64).  An array of more than
+    DUMP_WHOLE_MAX values is written as <name>_sample.npy instead: DUMP_SAMPLE of its flat values at fixed positions
+    (default_rng(0) without replacement, ascending) -- the whole directory stays under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_WHOLE_MAX:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], f"{name}_sample"
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     args = parse()
     launch_if_needed(args)
@@ -299,8 +330,9 @@ def main():
     # HIP events that time the stages live, inside the timed loop, on the launch stream.  They are created BEFORE the loop
     # (building one costs the host ~5-10 us, and the eager step is within 10 % of being host bound) and recorded on every
     # --event-every'th step only: [measured] round 3, 200 steps: 187.3 us/step with the records on every 4th step, 159.1 on
-    # every 50th -- a record is ~2.5 us of GPU time and the host work around it starves the queue.
-    _pool = [torch.cuda.Event(enable_timing=True) for _ in range(6 * (args.steps + 8))]
+    # every 50th -- a record is ~2.5 us of GPU time and the host work around it starves the queue.  (--full only: the
+    # headline needs no events, so a plain run records none.)
+    _pool = [torch.cuda.Event(enable_timing=True) for _ in range(6 * (args.steps + 8) if args.full else 0)]
     ev = lambda: _pool.pop() if _pool else torch.cuda.Event(enable_timing=True)  # noqa: E731
     conv_ev, vox_ev, conv_kev = [], [], []
     for e_ in _pool:   # (recorded once: torch creates the hipEvent_t at the first record -- sn_launch_timing_events needs the handle)
@@ -374,11 +406,12 @@ def main():
     # point of the timed loop; park everything allocated so far in the permanent generation
     gc.collect()
     gc.freeze()
-    # ---- cold figure first: W warm-up steps (lazy initialisation, allocator growth -- ~2 ms of GPU work after the
-    # seconds of idling the set-up above took), then K steps timed with the clocks wherever that leaves them
+    # ---- cold figure first (--full): W warm-up steps (lazy initialisation, allocator growth -- ~2 ms of GPU work after
+    # the seconds of idling the set-up above took), then K steps timed with the clocks wherever that leaves them
     for _ in range(args.warmup):
         step(False)
-    dt_cold, _ = timed_job(lambda: step(False), args.steps)
+    if args.full:
+        dt_cold, _ = timed_job(lambda: step(False), args.steps)
     # ---- headline: the chip's clocks take ~100 ms of sustained load to settle after idling ([measured] the same
     # kernels: 0.317 ms/launch in a 20-step run started cold, 0.296 in the second half of a 100-step run); the
     # untimed spin-up runs the same step until that much GPU time has passed, then the W warm-up steps follow
@@ -386,12 +419,13 @@ def main():
         spin(lambda: step(False), args.spinup_ms)
     for _ in range(args.warmup):
         step(False)
-    served_before = sna._hip.conv_i8_path_counts()[0]   # launches the folded int8 kernel has served so far
+    if args.full:
+        served_before = sna._hip.conv_i8_path_counts()[0]   # launches the folded int8 kernel has served so far
     event_every = args.event_every if args.event_every > 0 else (max(5, args.steps // 8) if args.steps >= 8 else 1)
     fence()
     t0 = time.perf_counter()
     for i_ in range(args.steps):
-        out = step(i_ % event_every == 0)   # HIP events around the stages: on every --event-every'th timed step
+        out = step(args.full and i_ % event_every == 0)   # (--full) HIP events around the stages: every --event-every'th step
     fence()
     dt_local = time.perf_counter() - t0
     dt = job_time_max(dt_local, dev)
@@ -401,6 +435,35 @@ def main():
         torch.distributed.all_gather_object(per_rank, B * args.steps / dt_local)
     else:
         per_rank = [B * args.steps / dt_local]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"head_out": out})   # [B,1,Z,X,Y] fp32: the step's result, the head per voxel
+
+    # which BASELINE config this run is (derived from the arguments, never assumed)
+    if (B, args.points, args.grid) == (32, 100_000, 64):
+        wl_tag = "C2"
+    elif args.grid == 128 and B == 32:
+        wl_tag = "C3 per-GPU share (256 tiles / 8 GPUs)"
+    else:
+        wl_tag = "custom"
+    G = sum(GENEO_NUM.values())
+    res = {
+        "metric": f"voxel-tiles/sec (point cloud -> {args.grid}^3 occupancy -> {G}-GENEO bank conv -> head)",
+        "value": tiles_done / dt, "unit": "tiles/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "i8", "data": "synthetic",
+        "clock_state": f"value: after {args.spinup_ms:.0f} ms untimed spin-up of the same step",
+        "rccl_ranks": rccl_ranks, "per_rank_tiles_per_s": per_rank,
+        "config": {"workload": f"{wl_tag}: {B} tiles/GPU x {args.points} points (fp64 xyz, UTM-scale), {args.grid}^3 voxel "
+                               f"grid, {G} GENEO kernels {KERNEL_SIZE[0]}^3 (cy 6, cone 5, neg 5); conv on the int8 "
+                               f"matrix cores: binary occupancy x 24-bit fixed-point weights (3 int8 digits), exact "
+                               f"int32 accumulation, fp32 head",
+                   "tiles_per_gpu": B, "points_per_tile": args.points, "grid": list(dims), "geneo_kernels": G,
+                   "kernel_size": list(KERNEL_SIZE), "parallelism": f"tile-sharded x{n_gpus}, no collectives"},
+    }
+    if not args.full:
+        finish(res, rank, world)
+        return
+
     # ---- the same job on the fp32 matrix pipe, end to end (K1 -> K2 -> fp32 conv + head), same loop, same fences
     n32 = max(3, min(10, args.steps))
     for _ in range(2):
@@ -419,7 +482,6 @@ def main():
     vox_ms = float(np.mean([a.elapsed_time(b) for a, b in vox_ev]))
     V = args.grid ** 3
     ntaps = int(np.prod(KERNEL_SIZE))
-    G = sum(GENEO_NUM.values())
     conv_flops = 2.0 * V * ntaps * G * B                  # 6.115 GFLOP/tile @ 64^3
     vox_bytes = (24.0 * args.points + 4.0 * V) * B        # 3.449 MB/tile @ (100k, 64^3)
     conv_tflops = conv_flops / (conv_ms * 1e-3) / 1e12
@@ -589,14 +651,6 @@ def main():
     if not args.no_extras and args.grid == 64:
         ref_defaults = reference_defaults_extra(sna, dev, ev, spin, args)
 
-    # which BASELINE config this run is (derived from the arguments, never assumed)
-    if (B, args.points, args.grid) == (32, 100_000, 64):
-        wl_tag = "C2"
-    elif args.grid == 128 and B == 32:
-        wl_tag = "C3 per-GPU share (256 tiles / 8 GPUs)"
-    else:
-        wl_tag = "custom"
-
     # ---- sustained figure: the same eager step, back to back, over >= --sustain-ms of wall time (no events inside):
     # long enough for an external sampler (rocm-smi, the driver's gpu_busy probe) to see the GPU busy, and a check on the
     # headline's clock state -- `value` is 20 steps = 3-4 ms
@@ -616,25 +670,14 @@ def main():
         with open(tpath) as f:
             traffic = json.load(f)
 
-    res = {
-        "metric": f"voxel-tiles/sec (point cloud -> {args.grid}^3 occupancy -> {G}-GENEO bank conv -> head)",
-        "value": tiles_done / dt, "unit": "tiles/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "i8", "data": "synthetic",
+    res.update({
         # the same K steps timed BEFORE the spin-up (clocks as the set-up left them), and the same job with the
         # contraction on the fp32 matrix pipe (K1 -> K2 -> conv_bank_kernel, same fences, same batch)
         "value_cold": tiles_done / dt_cold, "ms_per_step_cold": dt_cold / args.steps * 1e3,
         "value_fp32": B * n32 * n_gpus / dt_fp32, "ms_per_step_fp32": dt_fp32 / n32 * 1e3, "steps_fp32": n32,
         "value_sustained": sustained["value"] if sustained else None,
         "sustained": sustained,
-        "clock_state": f"value: after {args.spinup_ms:.0f} ms untimed spin-up of the same step; value_cold: none",
-        "rccl_ranks": rccl_ranks, "per_rank_tiles_per_s": per_rank,
-        "config": {"workload": f"{wl_tag}: {B} tiles/GPU x {args.points} points (fp64 xyz, UTM-scale), {args.grid}^3 voxel "
-                               f"grid, {G} GENEO kernels {KERNEL_SIZE[0]}^3 (cy 6, cone 5, neg 5); conv on the int8 "
-                               f"matrix cores: binary occupancy x 24-bit fixed-point weights (3 int8 digits), exact "
-                               f"int32 accumulation, fp32 head",
-                   "tiles_per_gpu": B, "points_per_tile": args.points, "grid": list(dims), "geneo_kernels": G,
-                   "kernel_size": list(KERNEL_SIZE), "parallelism": f"tile-sharded x{n_gpus}, no collectives"},
+        "clock_state": res["clock_state"] + "; value_cold: none",
         "points_per_s": B * args.points * n_gpus / (vox_ms * 1e-3),
         # dominant kernel.  `achieved` = ALGORITHMIC flops (2*V*729*16 per tile) / launch time; `peak` = dense int8
         # MFMA peak.  `executed` counts what the kernel really issues (3 digit planes x 64-slot steps): that is the
@@ -667,11 +710,16 @@ def main():
         "reference_defaults": ref_defaults,
         "graph_replay": graph_info,
         "skip_empty_tiles": skip_info,
-    }
+    })
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        res["cpu_baseline"] = cpu_baseline(args, specs, names, lambdas, last)
+        res["speedup_vs_cpu_fp64"] = res["value"] / res["cpu_baseline"]["value"]
+    finish(res, rank, world)
+
+
+def finish(res, rank, world):
+    """rank 0 prints the result line; a process group is taken down"""
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(args, specs, names, lambdas, last)
-            res["speedup_vs_cpu_fp64"] = res["value"] / res["cpu_baseline"]["value"]
         print(json.dumps(res), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

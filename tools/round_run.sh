@@ -7,15 +7,15 @@ O=gpurun_out/$TAG
 mkdir -p $O
 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest_gpu.txt 2>&1; tail -2 $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-python bench.py --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.err
 echo bench done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --sustain-ms 0 > $O/bench_profiled.json 2> $O/bench_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --sustain-ms 0 > $O/bench_profiled.json 2> $O/bench_profiled.err
 cp $(find $O/prof -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 rm -rf $O/prof
 echo kernel stats done
 # N = 2 through bench.py's own launcher, both ranks on this box's one GPU (gloo): the N > 1 code path, not a measurement
-python bench.py --gpus 2 --rehearse-on-one-gpu --steps 10 --warmup 2 --no-cpu-baseline --no-extras --sustain-ms 400 > $O/bench_rehearse2.json 2> $O/bench_rehearse2.err || echo "rehearsal failed"
-python bench.py --grid 128 --batch 32 --points 120000 --steps 10 --warmup 2 --no-cpu-baseline --sustain-ms 1500 > $O/c3_bench.json 2> $O/c3.err
+python bench.py --full --gpus 2 --rehearse-on-one-gpu --steps 10 --warmup 2 --no-cpu-baseline --no-extras --sustain-ms 400 > $O/bench_rehearse2.json 2> $O/bench_rehearse2.err || echo "rehearsal failed"
+python bench.py --full --grid 128 --batch 32 --points 120000 --steps 10 --warmup 2 --no-cpu-baseline --sustain-ms 1500 > $O/c3_bench.json 2> $O/c3.err
 python3 tools/train_step_bench.py --graph --iters 20 > $O/train_bench.txt 2>&1 || true
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_train -- python3 tools/train_step_bench.py --graph --iters 20 > $O/train_profiled.txt 2>&1 || true
 cp $(find $O/prof_train -name '*kernel_stats.csv' | head -1) $O/train_kernel_stats.csv || true
