@@ -11,8 +11,10 @@ OBJDIR   := build/obj
 CXXFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(SRC) -Wall -Wno-unused-function $(EXTRA)
 # voxel.hip reproduces numpy's fp64 rounding sequence: never contract a*b+c
 FLAGS_voxel := -ffp-contract=off
+# metrics.hip: the fp64 value arithmetic is metrics.py's binary_metric_values operation for operation
+FLAGS_metrics := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

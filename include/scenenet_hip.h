@@ -44,8 +44,10 @@ typedef enum {
  * experiments/scenenet_ts40k/defaults_config.yml:83-84): accepted as out_dtype of sn_conv_fused, as pred / grad
  * dtype of sn_loss_forward / sn_loss_backward and as the gradient dtype of sn_conv_corr_t; every sum stays fp32 / fp64.
  * SN_OCC8: uint8 grid whose values are all 0 or 1 (binary occupancy, torch.bool) -- lets sn_conv_bank use the
- * int8 matrix cores.  SN_U8 is a general 0..255 byte grid. */
-typedef enum { SN_F32 = 0, SN_F64 = 1, SN_U8 = 2, SN_OCC8 = 3, SN_BF16 = 4 } sn_dtype;
+ * int8 matrix cores.  SN_U8 is a general 0..255 byte grid.
+ * SN_I32: int32 labels (torch.int, what `y.to(torch.int)` gives): accepted as the target of sn_binary_stats only;
+ * every other entry rejects it. */
+typedef enum { SN_F32 = 0, SN_F64 = 1, SN_U8 = 2, SN_OCC8 = 3, SN_BF16 = 4, SN_I32 = 5 } sn_dtype;
 
 /* GENEO kinds: 0-2 = cylinderv2 / arrow / negSpherev2 of SceneNet (core/models/SCENE_Net.py:259-272);
  * 3-5 = cylinder_kernel / cone_kernel / neg_sphere_kernel of the v1 module SCENE_Net (SCENE_Net.py:158-170). */
@@ -539,6 +541,35 @@ int sn_criterion_backward(const void* pred, int pred_dtype, const void* gt, int 
                           const float* ranges, int H, const double* coef, const void* upstream, int up_dtype,
                           void* grad_pred, const float* pen_grad, int N, float* pen_out, sn_stream_t stream);
 
+
+/* ---------------------------------------------------------------------------
+ * K6 -- training metrics (csrc/metrics.hip)
+ * replaces: the torchmetrics 0.9 MetricCollection of init_metrics(tau) (utils/scripts_utils.py:80-91) that
+ *           LitSceneNet.{training,validation,test}_step call on every batch (core/lit_modules/lit_model_wrappers.py).
+ *
+ * One call counts a flattened binary prediction against its target:
+ *   predicted positive: pred >= tau in pred's dtype (tau rounded to it: fp32 0.65 -> 0.64999998f, bf16 -> 0.6484375);
+ *                       NaN is negative
+ *   target positive:    int(target) == 1 under C truncation (0.999 -> 0, 1.7 -> 1); a target whose truncation is
+ *                       neither 0 nor 1 (>= 2, <= -1, NaN, +-Inf, bytes > 1) is a BAD target
+ *   bad pred:           pred < 0 || pred > 1 (torchmetrics raises on it; the caller reads the counter)
+ * counts [SN_METRIC_NCOUNT] u64 = tp, fp, fn, tn, bad_pred, bad_target.
+ * values [SN_METRIC_NVALUE] f32 = JaccardIndex (macro mean of the two classes' IoU), Precision, Recall, F1Score,
+ * FBetaScore, computed in fp64 from the counts, 0/0 -> 0.
+ * ------------------------------------------------------------------------- */
+#define SN_METRIC_NCOUNT 6          /* tp, fp, fn, tn, bad_pred, bad_target */
+#define SN_METRIC_NVALUE 5          /* JaccardIndex, Precision, Recall, F1Score, FBetaScore */
+#define SN_METRIC_MAX_PARTS 1024
+#define SN_METRIC_WS_BYTES (SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8)
+
+/* pred [n] SN_F32 | SN_BF16 | SN_F64; target [n] SN_F32 | SN_F64 | SN_BF16 | SN_U8 | SN_OCC8 | SN_I32 (element-aligned
+ * pointers suffice: an unaligned head and tail are counted element by element).  tau in (0, 1), beta > 0.
+ * parts_ws: scratch of SN_METRIC_WS_BYTES (8-byte aligned).  state [NCOUNT] u64: caller-owned, ACCUMULATES this call's
+ * counts; batch [NCOUNT] u64 (nullable): this call's counts; values [2 x NVALUE] f32 (nullable): this call's values,
+ * then the values of the accumulated state.  Two launches (counting pass, one-workgroup combine), no atomics, no
+ * allocation, no synchronisation: capturable; the counts do not depend on launch order. */
+int sn_binary_stats(const void* pred, int pred_dtype, const void* target, int target_dtype, int64_t n, double tau,
+                    double beta, void* parts_ws, uint64_t* state, uint64_t* batch, float* values, sn_stream_t stream);
 
 
 #ifdef __cplusplus

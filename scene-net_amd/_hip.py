@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SN_HIP_LIB: another build of the same library (A/B timing of kernel variants); default: the in-tree build
 LIB_PATH = os.environ.get("SN_HIP_LIB") or os.path.join(_HERE, "lib", "libscenenet_hip.so")
 
-SN_F32, SN_F64, SN_U8, SN_OCC8, SN_BF16 = 0, 1, 2, 3, 4
+SN_F32, SN_F64, SN_U8, SN_OCC8, SN_BF16, SN_I32 = 0, 1, 2, 3, 4, 5
 SN_GENEO_CY, SN_GENEO_CONE, SN_GENEO_NEG = 0, 1, 2
 SN_GENEO_CY_V1, SN_GENEO_CONE_V1, SN_GENEO_NEG_V1 = 3, 4, 5
 SN_P_RADIUS, SN_P_SIGMA, SN_P_APEX, SN_P_CONE_RADIUS, SN_P_CONE_INC, SN_P_NEG_FACTOR = 0, 1, 2, 3, 4, 5
@@ -89,12 +89,15 @@ SYMBOLS = {
     "sn_criterion_forward": (c_int, [_P, _I, _P, _I, _I, ctypes.c_int64, _P, _P, _I, _I] + [ctypes.c_double] * 6
                              + [_P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
     "sn_criterion_backward": (c_int, [_P, _I, _P, _I, _I, ctypes.c_int64, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "sn_binary_stats": (c_int, [_P, _I, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
 SN_LOSS_MAX_BINS = 16
 SN_OCC_PARTS = 16
 SN_BBOX_PARTS = 32
+SN_METRIC_NCOUNT, SN_METRIC_NVALUE, SN_METRIC_MAX_PARTS = 6, 5, 1024
+SN_METRIC_WS_BYTES = SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -990,3 +993,34 @@ def param_penalty(P: torch.Tensor, mask: torch.Tensor, weight: float, with_sum: 
                                  int(bool(with_sum)), _ptr(value), _ptr(grad), _stream())
     _check(rc, "sn_param_penalty")
     return value, grad
+
+
+# --------------------------------------------------------------------------- #
+# sn_binary_stats only: int32 labels (`y.to(torch.int)` at the reference's call site) are a target dtype of this entry and
+# of no other, so the mapping lives here and not in _DT (every other wrapper keeps refusing int32 in Python)
+_METRIC_PRED_DT = {torch.float32: SN_F32, torch.bfloat16: SN_BF16, torch.float64: SN_F64}
+_METRIC_TGT_DT = {torch.float32: SN_F32, torch.float64: SN_F64, torch.bfloat16: SN_BF16, torch.uint8: SN_U8,
+                  torch.bool: SN_OCC8, torch.int32: SN_I32}
+
+
+@_on_tensor_device
+def binary_stats(pred: torch.Tensor, target: torch.Tensor, tau: float, beta: float, ws: torch.Tensor,
+                 state: torch.Tensor, batch: Optional[torch.Tensor] = None,
+                 values: Optional[torch.Tensor] = None) -> None:
+    """sn_binary_stats over pred / target flattened (same numel): adds this call's (tp, fp, fn, tn, bad_pred, bad_target)
+    to `state` [6] int64; `batch` [6] int64 (optional) receives them; `values` [10] f32 (optional) receives this call's
+    (JaccardIndex, Precision, Recall, F1Score, FBetaScore), then the accumulated state's.  ws: int64 scratch of
+    SN_METRIC_WS_BYTES.  Two launches on the current stream, no synchronisation."""
+    if pred.numel() != target.numel():
+        raise ValueError(f"pred ({pred.numel()} elements) and target ({target.numel()} elements) must have the same size")
+    if pred.dtype not in _METRIC_PRED_DT:
+        raise HipLibraryError(f"pred must be float32, bfloat16 or float64 (got {pred.dtype})")
+    if target.dtype not in _METRIC_TGT_DT:
+        raise HipLibraryError(f"target must be float32, float64, bfloat16, uint8, bool or int32 (got {target.dtype})")
+    if ws.numel() * ws.element_size() < SN_METRIC_WS_BYTES:
+        raise HipLibraryError(f"ws must hold {SN_METRIC_WS_BYTES} bytes")
+    rc = load().sn_binary_stats(_ptr(pred, None, "pred"), _METRIC_PRED_DT[pred.dtype], _ptr(target, None, "target"),
+                                _METRIC_TGT_DT[target.dtype], int(pred.numel()), float(tau), float(beta), _ptr(ws, None, "ws"),
+                                _ptr(state, torch.int64, "state"), _ptr(batch, torch.int64, "batch"),
+                                _ptr(values, torch.float32, "values"), _stream())
+    _check(rc, "sn_binary_stats")

@@ -82,15 +82,22 @@ class CapturedTrainingStep:
     """step = zero_grad; grids = pipe.voxelize(batch, want_gt=True); loss = criterion(model(grids.occ), grids.gt_occ,
     cvx coefficients, GENEO parameters); loss.backward(); [all-reduce of the gradients over `group`]; optimizer.step().
     `replay()` runs it on whatever the batch's device buffers hold and returns the (static) loss tensor of THIS rank's
-    tiles.  With a process group of more than one rank every rank must build and replay the step together."""
+    tiles.  With a process group of more than one rank every rank must build and replay the step together.
+
+    metrics (a BinarySegmentationMetrics, optional): updated with (pred, grids.gt_occ) after the criterion, inside the
+    graph; its state is reset once the warm-up steps and the capture are done, so from then on each replay adds exactly
+    that step's counts (metrics.compute() once per epoch, metrics.reset() between epochs).  `step.pred` / `step.target`
+    are the step's static prediction and ground-truth grids: after a replay they hold that replay's."""
 
     def __init__(self, pipe: ScenePipeline, criterion: Callable, optimizer: torch.optim.Optimizer, batch: PointBatch,
-                 warmup: int = 3, loss_fn: Optional[Callable] = None, group=None):
+                 warmup: int = 3, loss_fn: Optional[Callable] = None, group=None, metrics=None):
         import torch.distributed as dist
         live = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if live else 1
         self.group = group
         self.pipe, self.criterion, self.optimizer, self.batch = pipe, criterion, optimizer, batch
+        self.metrics = metrics
+        self.pred = self.target = None
         model = pipe.model
         params = [p for p in model.parameters() if p.requires_grad]
 
@@ -101,6 +108,9 @@ class CapturedTrainingStep:
                 loss = loss_fn(pred, grids)
             else:
                 loss = criterion(pred, grids.gt_occ, model.get_cvx_coefficients(), model.get_geneo_params())
+            self.pred, self.target = pred.detach(), grids.gt_occ
+            if metrics is not None:
+                metrics.update(self.pred, self.target)
             backward_seeded(loss)
             return loss
 
@@ -136,6 +146,8 @@ class CapturedTrainingStep:
             self.graph_opt = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_opt, pool=self.graph.pool(), capture_error_mode=mode):
                 optimizer.step()
+        if metrics is not None:   # the warm-up steps were counted too: from here on, replays only
+            metrics.reset()
 
     def replay(self) -> torch.Tensor:
         self.graph.replay()
