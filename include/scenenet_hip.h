@@ -94,29 +94,46 @@ const char* sn_last_error(void);
 /* Number of gfx950 devices visible (0 when none); never throws. */
 int sn_device_count(void);
 
-/* Process-wide options.
- *   "conv_skip_empty_tiles" (default 0): sn_conv_bank on SN_OCC8 input skips the MFMA steps of workgroup tiles whose
+/* Process-wide options (csrc/cabi.hip keeps them in one table, in this order).  A switch stores any value != 0 as 1; every
+ * other option takes the range given with it.  sn_set_option returns SN_ERR_INVALID_ARG for a null or unknown name or a
+ * value out of range (and changes nothing); sn_get_option returns -1 for a null or unknown name.  An option listed with an
+ * environment variable reads it ONCE, the first time the option is looked at (never per call); only its first character
+ * counts, '1' giving the value shown; an sn_set_option before that first look wins, and the variable is then never read.
+ *   "conv_skip_empty_tiles" (switch, default 0): sn_conv_bank on SN_OCC8 input skips the MFMA steps of workgroup tiles whose
  *       halo holds no set voxel (their response is exactly 0 for every kernel).  Output unchanged; run time becomes
  *       data dependent, so benchmarks quote it separately from the dense figure.
- *   "conv_i8_tolerance_ppb" (default 90000 = 9e-5): the int8 kernels (sn_conv_bank / sn_conv_fused / sn_forward_auto on
+ *   "conv_i8_tolerance_ppb" (>= 0, default 90000 = 9e-5): the int8 kernels (sn_conv_bank / sn_conv_fused / sn_forward_auto on
  *       binary occupancy) quantise the weights to 24-bit fixed point and compute, on the device, the exact worst case
  *       of the resulting activation error over all binary inputs.  A bank whose bound exceeds value * 1e-9 is computed
  *       by the fp32 kernel instead (decided on the device, no host synchronisation).  0 switches the guard off.
- *   "conv_i8_fold" (default 1): 9 x 9 x 9 banks that are bit-for-bit symmetric in x and y (every GENEO bank) are
- *       contracted over 9 x 5 x 5 folded taps (exactly the same integer sums, a third of the MFMAs); the symmetry is
- *       checked on the device at every call, other banks take the unfolded kernel; 0 = never try
- *   "conv_i8_legacy" (default 0): 1 = sn_conv_bank uses the four-copy int8 kernel (conv_i8.hip) for every shape
- *       instead of the stride-4 kernel (conv_i8s.hip) it prefers for ky = 9 (A/B timing, parity tests of both).
- *   "conv_i8z_variant" (default 2): the shape of the z-walk's tickets -- 0: rounds of two x-rows on 8 waves, 1: one round of
- *       one x-row per ticket on 12 waves, 2: two such rounds per ticket.  Same results bit for bit (tested on all three).
- *   "voxel_onepass" (default 1): sn_voxel_occupancy_fused[_bank] on grids whose bitmap(s) fit one workgroup's LDS (64^3)
- *       read the points ONCE -- bounding box, descriptor and binning in one launch whose workgroups exchange partial boxes;
- *       0 = the two-kernel form (box pass, then binning pass).  Same results bit for bit.
- *   "voxel_onepass_spin" (default 64): polls (~1 us each) a workgroup of that launch waits for its tile's other workgroups
- *       before it computes the tile's box from the points alone (same bits; 0 = never wait).
- *   "conv_i8z_inject_fault" (default 0): TEST HOOK.  1 = the next z-walk launches never report plane 0's first raw rows
- *       as landed, so a dependency spin gives up (~0.5 s per launch): the way to see the loud failure path -- NaN outputs
- *       and the sticky device status -- on the product build (tests/test_gpu_conv_zwalk.py). */
+ *   "conv_i8_fold" (switch, default 1; SN_CONV_I8_NOFOLD=1 gives 0): 9 x 9 x 9 banks that are bit-for-bit symmetric in x and
+ *       y (every GENEO bank) are contracted over 9 x 5 x 5 folded taps (exactly the same integer sums, a third of the
+ *       MFMAs); the symmetry is checked on the device at every call, other banks take the unfolded kernel; 0 = never try
+ *   "conv_i8_legacy" (switch, default 0; SN_CONV_I8_LEGACY=1 gives 1): 1 = sn_conv_bank uses the four-copy int8 kernel
+ *       (conv_i8.hip) for every shape instead of the stride-4 kernel (conv_i8s.hip) it prefers for ky = 9 (A/B timing,
+ *       parity tests of both).
+ *   "conv_i8_no_stage" (switch, default 0; SN_CONV_I8_NO_STAGE=1 gives 1): 1 = the four-copy int8 kernel without its LDS-DMA
+ *       staging.
+ *   "conv_i8z_variant" (0 .. 2, default 2): the shape of the z-walk's tickets -- 0: rounds of two x-rows on 8 waves, 1: one
+ *       round of one x-row per ticket on 12 waves, 2: two such rounds per ticket.  Same results bit for bit (tested on all
+ *       three).
+ *   "conv_no_i8" (switch, default 0; SN_CONV_NO_I8=1 gives 1): 1 = sn_conv_bank runs binary occupancy through the fp32
+ *       kernel, never the int8 ones.
+ *   "conv_double_buffer" (switch, default 0; SN_CONV_DOUBLE_BUFFER=1 gives 1): 1 = the fp32 kernel of sn_conv_bank on
+ *       double-buffered 4 x 4 x 64 tiles instead of single-buffered 8 x 8 x 64 ones.
+ *   "conv_lin_no24" (switch, default 0; SN_CONV_LIN_NO24=1 gives 1): 1 = sn_conv_fused packs its kernel rows in 32 bytes
+ *       even where 24 would do.  Same results bit for bit.
+ *   "voxel_onepass" (switch, default 1): sn_voxel_occupancy_fused[_bank] on grids whose bitmap(s) fit one workgroup's LDS
+ *       (64^3) read the points ONCE -- bounding box, descriptor and binning in one launch whose workgroups exchange partial
+ *       boxes; 0 = the two-kernel form (box pass, then binning pass).  Same results bit for bit.
+ *   "voxel_onepass_spin" (>= 0, default 64): polls (~1 us each) a workgroup of that launch waits for its tile's other
+ *       workgroups before it computes the tile's box from the points alone (same bits; 0 = never wait).
+ *   "corr_dense" (switch, default 0; SN_CORR_DENSE=1 gives 1): 1 = the backward correlation of binary occupancy
+ *       (sn_conv_corr*) as the GEMM form (K4) instead of the gather over the set voxels (K4s).
+ *   "corr_sparse_tile_bytes" (0 .. 2048, default 0): input bytes per job of that gather (0: 2048, the maximum).
+ *   "conv_i8z_inject_fault" (switch, default 0): TEST HOOK.  1 = the next z-walk launches never report plane 0's first raw
+ *       rows as landed, so a dependency spin gives up (~0.5 s per launch): the way to see the loud failure path -- NaN
+ *       outputs and the sticky device status -- on the product build (tests/test_gpu_conv_zwalk.py). */
 int sn_set_option(const char* name, int value);
 int sn_get_option(const char* name);
 

@@ -5,6 +5,7 @@ device, the call raises.  PyTorch is used only for device memory and streams.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import functools
 import os
@@ -161,6 +162,25 @@ def set_option(name: str, value: int) -> None:
 
 def get_option(name: str) -> int:
     return int(load().sn_get_option(name.encode()))
+
+
+@contextlib.contextmanager
+def options(**values: int):
+    """`with options(conv_i8_legacy=1): ...` sets library options for the block and then puts back the values it found, in
+    reverse order, on an exception as well.  An unknown name raises before anything is changed."""
+    found = []
+    for name in values:
+        old = get_option(name)
+        if old == -1:
+            raise HipLibraryError(f"sn_get_option: unknown option '{name}'")
+        found.append((name, old))
+    try:
+        for name, value in values.items():
+            set_option(name, value)
+        yield
+    finally:
+        for name, old in reversed(found):
+            set_option(name, old)
 
 
 def conv_i8_path_counts() -> Tuple[int, int, int]:

@@ -1,7 +1,8 @@
 // C-ABI housekeeping: version, last-error text, device probe.
 #include "common.h"
-#include <cstring>
+#include <climits>
 #include <cstdlib>
+#include <cstring>
 
 #include <atomic>
 #include <mutex>
@@ -12,62 +13,45 @@ char* error_buffer() {
     static thread_local char buf[512] = {0};
     return buf;
 }
-static std::atomic<int> g_skip_empty{0};
-int option_conv_skip_empty_tiles() { return g_skip_empty.load(std::memory_order_relaxed); }
-static std::atomic<int> g_i8_legacy{-1};   // -1: not looked at yet; SN_CONV_I8_LEGACY=1 in the environment starts it at 1
-int option_conv_i8_legacy() {
-    int v = g_i8_legacy.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("SN_CONV_I8_LEGACY");
-        int expected = -1;
-        g_i8_legacy.compare_exchange_strong(expected, (e && e[0] == '1') ? 1 : 0, std::memory_order_relaxed);
-        v = g_i8_legacy.load(std::memory_order_relaxed);
-    }
-    return v;
-}
-static std::atomic<int> g_vox_onepass{1};
-int option_voxel_onepass() { return g_vox_onepass.load(std::memory_order_relaxed); }
-static std::atomic<int> g_vox_spin{64};
-int option_voxel_onepass_spin() { return g_vox_spin.load(std::memory_order_relaxed); }
-static std::atomic<int> g_i8z_fault{0};
-int option_conv_i8z_inject_fault() { return g_i8z_fault.load(std::memory_order_relaxed); }
-static std::atomic<int> g_i8z_variant{2};
-int option_conv_i8z_variant() { return g_i8z_variant.load(std::memory_order_relaxed); }
-static std::atomic<int> g_corr_tile_bytes{0};
-int option_corr_sparse_tile_bytes() { return g_corr_tile_bytes.load(std::memory_order_relaxed); }
-static std::atomic<int> g_i8_fold{-1};   // -1: not looked at yet; SN_CONV_I8_NOFOLD=1 in the environment starts it at 0
-int option_conv_i8_fold() {
-    int v = g_i8_fold.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("SN_CONV_I8_NOFOLD");
-        int expected = -1;
-        g_i8_fold.compare_exchange_strong(expected, (e && e[0] == '1') ? 0 : 1, std::memory_order_relaxed);
-        v = g_i8_fold.load(std::memory_order_relaxed);
-    }
-    return v;
-}
-
-
+// The options, in the order of sn::Opt (common.h); include/scenenet_hip.h documents each one.  A switch stores value != 0;
+// any other option takes lo .. hi (every range starts at 0: a stored value is never negative).  An option with a variable
+// starts at -1, "not looked at yet": the first look stores `on` if the variable's first character is '1', else the default.
 namespace {
-struct ExtraOpt {
+struct Option {
     const char* name;
-    const char* env;
-    std::atomic<int> value;   // -1: not looked at yet (the environment decides at first use)
+    const char* env;   // nullptr: no variable
+    int on;            // what the variable gives when its first character is '1'
+    int def, lo, hi;
+    bool is_switch;
+    std::atomic<int> value{env ? -1 : def};
 };
-ExtraOpt g_extra[kOptCount] = {{"conv_no_i8", "SN_CONV_NO_I8", {-1}},
-                               {"conv_double_buffer", "SN_CONV_DOUBLE_BUFFER", {-1}},
-                               {"conv_lin_no24", "SN_CONV_LIN_NO24", {-1}},
-                               {"conv_i8_no_stage", "SN_CONV_I8_NO_STAGE", {-1}},
-                               {"corr_dense", "SN_CORR_DENSE", {-1}}};
+Option g_options[] = {
+    // name                    variable                 on  default  lo  hi       switch
+    {"conv_skip_empty_tiles",  nullptr,                 0,  0,       0,  1,       true},
+    {"conv_i8_tolerance_ppb",  nullptr,                 0,  90000,   0,  INT_MAX, false},   // 9e-5: the 1e-4 bar less fp32 roundings
+    {"conv_i8_fold",           "SN_CONV_I8_NOFOLD",     0,  1,       0,  1,       true},
+    {"conv_i8_legacy",         "SN_CONV_I8_LEGACY",     1,  0,       0,  1,       true},
+    {"conv_i8_no_stage",       "SN_CONV_I8_NO_STAGE",   1,  0,       0,  1,       true},
+    {"conv_i8z_variant",       nullptr,                 0,  2,       0,  2,       false},
+    {"conv_no_i8",             "SN_CONV_NO_I8",         1,  0,       0,  1,       true},
+    {"conv_double_buffer",     "SN_CONV_DOUBLE_BUFFER", 1,  0,       0,  1,       true},
+    {"conv_lin_no24",          "SN_CONV_LIN_NO24",      1,  0,       0,  1,       true},
+    {"voxel_onepass",          nullptr,                 0,  1,       0,  1,       true},
+    {"voxel_onepass_spin",     nullptr,                 0,  64,      0,  INT_MAX, false},
+    {"corr_dense",             "SN_CORR_DENSE",         1,  0,       0,  1,       true},
+    {"corr_sparse_tile_bytes", nullptr,                 0,  0,       0,  2048,    false},
+    {"conv_i8z_inject_fault",  nullptr,                 0,  0,       0,  1,       true},
+};
+static_assert(sizeof(g_options) / sizeof(g_options[0]) == kOptCount, "one entry per sn::Opt");
 }  // namespace
-int option_extra(ExtraOption which) {
-    ExtraOpt& o = g_extra[which];
+
+int option(Opt which) {
+    Option& o = g_options[which];
     int v = o.value.load(std::memory_order_relaxed);
     if (v < 0) {
         const char* e = getenv(o.env);
-        v = (e && e[0] == '1') ? 1 : 0;
         int expected = -1;
-        o.value.compare_exchange_strong(expected, v, std::memory_order_relaxed);
+        o.value.compare_exchange_strong(expected, (e && e[0] == '1') ? o.on : o.def, std::memory_order_relaxed);
         v = o.value.load(std::memory_order_relaxed);
     }
     return v;
@@ -86,11 +70,6 @@ GateScope::~GateScope() {
     g_gate.ptr[slot_] = nullptr;
     g_gate.want[slot_] = 0;
 }
-
-// tolerance of the int8 kernels' quantisation guard, in units of 1e-9 (default 90 000 = 9e-5: the 1e-4 parity bar
-// less the fp32 roundings of the recombination)
-static std::atomic<int> g_i8_tol_ppb{90000};
-float option_conv_i8_tolerance() { return 1e-9f * (float)g_i8_tol_ppb.load(std::memory_order_relaxed); }
 
 // Flag / ticket words for the launches that need one int of device memory.  Two pools per device, allocated together
 // the first time (sn_prepare_device, or the first call -- which must then be outside a stream capture):
@@ -205,68 +184,21 @@ hipError_t ensure_dynamic_lds(const void* kernel, int bytes) {
 
 extern "C" int sn_set_option(const char* name, int value) {
     if (!name) return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: null name");
-    if (strcmp(name, "conv_skip_empty_tiles") == 0) {
-        sn::g_skip_empty.store(value ? 1 : 0, std::memory_order_relaxed);
+    for (auto& o : sn::g_options) {
+        if (strcmp(name, o.name) != 0) continue;
+        if (o.is_switch)
+            value = value != 0;
+        else if (value < o.lo || value > o.hi)
+            return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: %s takes %d .. %d", name, o.lo, o.hi);
+        o.value.store(value, std::memory_order_relaxed);
         return SN_OK;
     }
-    if (strcmp(name, "conv_i8_tolerance_ppb") == 0) {
-        if (value < 0) return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: conv_i8_tolerance_ppb must be >= 0");
-        sn::g_i8_tol_ppb.store(value, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "conv_i8_legacy") == 0) {
-        sn::g_i8_legacy.store(value ? 1 : 0, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "conv_i8_fold") == 0) {
-        sn::g_i8_fold.store(value ? 1 : 0, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "voxel_onepass") == 0) {
-        sn::g_vox_onepass.store(value ? 1 : 0, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "voxel_onepass_spin") == 0) {
-        if (value < 0) return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: voxel_onepass_spin must be >= 0");
-        sn::g_vox_spin.store(value, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "conv_i8z_inject_fault") == 0) {
-        sn::g_i8z_fault.store(value ? 1 : 0, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "conv_i8z_variant") == 0) {
-        if (value < 0 || value > 2) return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: conv_i8z_variant is 0, 1 or 2");
-        sn::g_i8z_variant.store(value, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    if (strcmp(name, "corr_sparse_tile_bytes") == 0) {
-        if (value < 0 || value > 2048)
-            return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: corr_sparse_tile_bytes is 0 (default: 2048) .. 2048");
-        sn::g_corr_tile_bytes.store(value, std::memory_order_relaxed);
-        return SN_OK;
-    }
-    for (auto& o : sn::g_extra)
-        if (strcmp(name, o.name) == 0) {
-            o.value.store(value ? 1 : 0, std::memory_order_relaxed);
-            return SN_OK;
-        }
     return sn::fail(SN_ERR_INVALID_ARG, "sn_set_option: unknown option '%s'", name);
 }
 
 extern "C" int sn_get_option(const char* name) {
-    if (name && strcmp(name, "conv_skip_empty_tiles") == 0) return sn::option_conv_skip_empty_tiles();
-    if (name && strcmp(name, "conv_i8_tolerance_ppb") == 0) return sn::g_i8_tol_ppb.load(std::memory_order_relaxed);
-    if (name && strcmp(name, "conv_i8_legacy") == 0) return sn::option_conv_i8_legacy();
-    if (name && strcmp(name, "conv_i8_fold") == 0) return sn::option_conv_i8_fold();
-    if (name && strcmp(name, "conv_i8z_variant") == 0) return sn::option_conv_i8z_variant();
-    if (name && strcmp(name, "conv_i8z_inject_fault") == 0) return sn::option_conv_i8z_inject_fault();
-    if (name && strcmp(name, "voxel_onepass") == 0) return sn::option_voxel_onepass();
-    if (name && strcmp(name, "voxel_onepass_spin") == 0) return sn::option_voxel_onepass_spin();
-    if (name && strcmp(name, "corr_sparse_tile_bytes") == 0) return sn::option_corr_sparse_tile_bytes();
-    if (name)
-        for (int i = 0; i < sn::kOptCount; ++i)
-            if (strcmp(name, sn::g_extra[i].name) == 0) return sn::option_extra((sn::ExtraOption)i);
+    for (int i = 0; name && i < sn::kOptCount; ++i)
+        if (strcmp(name, sn::g_options[i].name) == 0) return sn::option(static_cast<sn::Opt>(i));
     return -1;
 }
 

@@ -28,14 +28,31 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(sn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-int option_conv_skip_empty_tiles();  // cabi.hip (sn_set_option)
-int option_conv_i8_fold();            // cabi.hip (sn_set_option "conv_i8_fold", default 1): 0 = never try the folded int8 kernel (conv_i8s.hip)
-int option_voxel_onepass();           // cabi.hip (sn_set_option "voxel_onepass", default 1): 0 = the two-kernel form (bbox, then binning) on every grid
-int option_voxel_onepass_spin();      // cabi.hip (sn_set_option "voxel_onepass_spin", default 64): polls of the box exchange before a workgroup goes alone
-int option_conv_i8z_inject_fault();   // cabi.hip (sn_set_option "conv_i8z_inject_fault"): test hook, see conv_i8z.inc's prologue
-int option_conv_i8z_variant();        // cabi.hip (sn_set_option "conv_i8z_variant"): shape of the z-walk kernel's rounds (conv_i8z.inc)
-int option_corr_sparse_tile_bytes();  // cabi.hip (sn_set_option "corr_sparse_tile_bytes"): input bytes per job of the sparse correlation (0: 2048, the maximum)
-int option_conv_i8_legacy();          // cabi.hip (sn_set_option "conv_i8_legacy"): 1 = the four-copy kernel of conv_i8.hip for every shape
+// Process-wide runtime options (sn_set_option / sn_get_option): one entry each, in this order, in cabi.hip's option table
+// (name, environment variable, default, range); include/scenenet_hip.h documents what each one does.
+enum Opt {
+    kOptConvSkipEmptyTiles,
+    kOptConvI8TolerancePpb,
+    kOptConvI8Fold,
+    kOptConvI8Legacy,
+    kOptConvI8NoStage,
+    kOptConvI8zVariant,
+    kOptConvNoI8,
+    kOptConvDoubleBuffer,
+    kOptConvLinNo24,
+    kOptVoxelOnepass,
+    kOptVoxelOnepassSpin,
+    kOptCorrDense,
+    kOptCorrSparseTileBytes,
+    kOptConvI8zInjectFault,
+    kOptCount
+};
+// A relaxed atomic load.  An option with a variable reads it ONCE, at the first look (never per call: an environment
+// lookup per launch sat on the production dispatch, and a stray variable could change kernels mid-run); an sn_set_option
+// before that look wins.
+int option(Opt which);   // cabi.hip
+// the int8 kernels' quantisation guard compares its bound against exactly this float (0: guard off)
+inline float conv_i8_tolerance() { return 1e-9f * (float)option(kOptConvI8TolerancePpb); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize, set once per kernel (and raised when a launch needs more): the
 // attribute call is not a stream operation, so steady-state launches stay free of it (cheaper, graph-capturable).
@@ -65,19 +82,7 @@ struct GateScope {
     int slot_;
 };
 
-// Result-preserving switches beside the named accessors above: set with sn_set_option(name, v); the environment variable
-// listed with each is read ONCE, the first time the option is looked at (never per call: a getenv per launch sat on the
-// production dispatch, and a stray variable could change kernels mid-run).
-enum ExtraOption {
-    kOptConvNoI8 = 0,        // "conv_no_i8"        SN_CONV_NO_I8=1         binary occupancy through the fp32 kernel
-    kOptConvDoubleBuffer,    // "conv_double_buffer" SN_CONV_DOUBLE_BUFFER=1 fp32 kernel: double-buffered 4x4x64 tiles
-    kOptConvLinNo24,         // "conv_lin_no24"     SN_CONV_LIN_NO24=1      K3L: 32-byte instead of 24-byte kernel rows
-    kOptConvI8NoStage,       // "conv_i8_no_stage"  SN_CONV_I8_NO_STAGE=1   four-copy kernel without the LDS-DMA staging
-    kOptCorrDense,           // "corr_dense"        SN_CORR_DENSE=1         backward correlation of binary occupancy as the GEMM (K4) instead of the gather (K4s)
-    kOptCount
-};
-int option_extra(ExtraOption which);   // cabi.hip
-// The kernels' side of those switches: SN_DBG(shape, bit) is a COMPILE-TIME false in the product build -- no kernel carries
+// Debug bits of a kernel's shape: SN_DBG(shape, bit) is a COMPILE-TIME false in the product build -- no kernel carries
 // a runtime test of a debug word; in a -DSN_CONV_DEBUG build it reads the shape's dbg field.
 #ifdef SN_CONV_DEBUG
 #define SN_DBG(shape, bit) (((shape).dbg & (bit)) != 0)
@@ -122,7 +127,6 @@ __device__ __forceinline__ void sticky_latch(int32_t* sticky, int code, int a, i
     }
 }
 
-float option_conv_i8_tolerance();   // cabi.hip (sn_set_option "conv_i8_tolerance_ppb"): 0 = quantisation guard off
 // One int of device memory per call (the flag an int8 launch leaves for the gated fp32 launch enqueued behind it, dynamic
 // tile tickets): from a recycled ring for eager launches, from a never-recycled pool while `stream` is capturing
 // (cabi.hip).  nullptr if the pool cannot be allocated.

@@ -112,9 +112,9 @@ int sn::conv_bank_group(const void* x, int x_dtype, const float* bank, const flo
 
     if (x_dtype == SN_OCC8) {
         // binary occupancy bytes: int8 matrix cores (exact integer accumulation of 24-bit fixed-point weights)
-        if (!sn::option_extra(sn::kOptConvNoI8)) {
+        if (!sn::option(sn::kOptConvNoI8)) {
             // ky = 9: the stride-4 kernel (one halo copy, 12 MFMA steps); everything else: the four-copy kernel
-            if (!sn::option_conv_i8_legacy()) {
+            if (!sn::option(sn::kOptConvI8Legacy)) {
                 const int rs = sn::conv_occ_i8s((const uint8_t*)x, bank, lambdas, B, Z, X, Y, G, Gtot, g0, head, kz, kx, ky,
                                                 act, out, out_dtype, sn::as_stream(stream));
                 if (rs <= 0) return rs;
@@ -131,7 +131,7 @@ int sn::conv_bank_group(const void* x, int x_dtype, const float* bank, const flo
     // Preferred when asked for (sn_set_option "conv_double_buffer"): double-buffered halo.  [measured, C2] the single-buffer
     // 8x8x64 tile (4 rounds per wave between barriers, waves drift apart so one wave's epilogue overlaps its SIMD partner's
     // MFMAs) runs 127.7 TF; the double-buffered 4x4x64 tile (1 round per wave per barrier) 118.5 TF: opt-in.
-    if (!plan_fp32(s, B, Z, X, Y, G, Gtot, g0, head, kz, kx, ky, num_cus(), sn::option_extra(sn::kOptConvDoubleBuffer) != 0, dbl))
+    if (!plan_fp32(s, B, Z, X, Y, G, Gtot, g0, head, kz, kx, ky, num_cus(), sn::option(sn::kOptConvDoubleBuffer) != 0, dbl))
         return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_bank: kernel %dx%dx%d does not fit the 160 KiB LDS tile", kz, kx,
                         ky);
     hipStream_t st = sn::as_stream(stream);

@@ -702,8 +702,8 @@ int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B
     s.delta = s.PYA - py;
     s.nyt = (Y + TY - 1) / TY;
     s.dbg = sn::debug_env_int("SN_CONV_I8_DBG");   // (0 in the product: common.h)
-    s.skip_empty = sn::option_conv_skip_empty_tiles();
-    const bool nostage = sn::option_extra(sn::kOptConvI8NoStage) != 0;
+    s.skip_empty = sn::option(sn::kOptConvSkipEmptyTiles);
+    const bool nostage = sn::option(sn::kOptConvI8NoStage) != 0;
     const int cus = num_cus();
     const int need = s.delta + 15 + 48 + 4 * s.C + 3;  // bytes of a halo row the reads can touch
     // variants in order of preference: (row stride, LDS-DMA staging)
@@ -756,7 +756,7 @@ int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B
                 ticket = nullptr;  // static order still gives the right answer
             }
         }
-        s.tol = sn::option_conv_i8_tolerance();
+        s.tol = sn::conv_i8_tolerance();
         s.route = nullptr;
         if (s.tol > 0.0f) {
             s.route = sn::device_flag_slot(stream);

@@ -176,7 +176,7 @@ int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int 
     if (ky != 9 || kz * kx != 81 || Y % 16 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || G > 16) return 1;
     if (act && (reinterpret_cast<uintptr_t>(act) & 15)) return 1;
     if (out && (reinterpret_cast<uintptr_t>(out) & 15)) return 1;
-    if (sn::option_conv_skip_empty_tiles()) return 1;   // data-dependent tile skipping lives in conv_i8.hip
+    if (sn::option(sn::kOptConvSkipEmptyTiles)) return 1;   // data-dependent tile skipping lives in conv_i8.hip
     Shape s;
     memset(&s, 0, sizeof(s));
     s.B = B; s.Z = Z; s.X = X; s.Y = Y; s.G = G; s.kz = kz; s.kx = kx;
@@ -192,12 +192,12 @@ int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int 
     const bool found = plan_stride4(s, B, Z, X, Y, kz, kx, cus);
     if (!found) return 1;
     // quantisation guard (see the header): tolerance on the worst-case activation error of the int8 path
-    s.tol = sn::option_conv_i8_tolerance();
+    s.tol = sn::conv_i8_tolerance();
     const int grid = cus < s.ntiles ? cus : s.ntiles;
     // 1. the folded kernel (banks symmetric in x and y: every GENEO bank) -- it checks the symmetry on the device, runs the
     //    stride-4 body itself for a bank that is not, and leaves *flag = 0 (served) or 1 (bound exceeded: fp32 kernel)
     int32_t* flag = sn::device_flag_slot(stream);
-    const bool fold = kz == 9 && kx == 9 && flag && sn::option_conv_i8_fold() &&
+    const bool fold = kz == 9 && kx == 9 && flag && sn::option(sn::kOptConvI8Fold) &&
                       s.dbg == 0;   // (the debug switches belong to the stride-4 kernel)
     bool folded = false;
     if (fold) {
@@ -269,7 +269,7 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
     if (act && (reinterpret_cast<uintptr_t>(act) & 15)) return 1;
     if (out && (reinterpret_cast<uintptr_t>(out) & 15)) return 1;
     if (!prep || (reinterpret_cast<uintptr_t>(prep) & 15)) return 1;
-    if (sn::option_conv_skip_empty_tiles() || !sn::option_conv_i8_fold() || sn::option_conv_i8_legacy()) return 1;
+    if (sn::option(sn::kOptConvSkipEmptyTiles) || !sn::option(sn::kOptConvI8Fold) || sn::option(sn::kOptConvI8Legacy)) return 1;
     const int cus = num_cus();
     // the stride-4 kernel's plan: what the launch runs, in place, for a bank that is not symmetric
     Shape s4;
@@ -280,7 +280,7 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
     s4.nyt = (Y + TY - 1) / TY;
     s4.dynamic = 1;
     if (!plan_stride4(s4, B, Z, X, Y, kz, kx, cus)) return 1;
-    s4.tol = sn::option_conv_i8_tolerance();
+    s4.tol = sn::conv_i8_tolerance();
     s4.route = nullptr;   // (the fallback launch reads the walk's verdict; the body must not rewrite it under other workgroups)
     int32_t* const route = reinterpret_cast<int32_t*>(prep + kPrepRoute);
     fp32k::ConvShape cs;
@@ -292,7 +292,7 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
     z.gate = s4.gate;
     z.tol = s4.tol;
     z.route = route;
-    z.dbg = sn::option_conv_i8z_inject_fault() ? 1 : 0;
+    z.dbg = sn::option(sn::kOptConvI8zInjectFault) ? 1 : 0;
     z.served = assume_served ? 1 : 0;
     z.sticky = sn::sticky_device_ptr(stream);
     s4.sticky = z.sticky;
@@ -351,7 +351,7 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
     } while (0)
     // the shape of a ticket: rounds of two x-rows on 8 waves (2 per SIMD, the tile kernels' round), or rounds of one
     // x-row -- half the accumulator registers -- on 12 waves (3 per SIMD), one or two of them per ticket
-    switch (sn::option_conv_i8z_variant()) {
+    switch (sn::option(sn::kOptConvI8zVariant)) {
         case 0: SN_LAUNCH_I8Z_V(2, 1, 8); break;
         case 1: SN_LAUNCH_I8Z_V(1, 1, 12); break;
         default: SN_LAUNCH_I8Z_V(1, 2, 12); break;

@@ -510,7 +510,7 @@ int sn::conv_fused_lin(const uint8_t* x, const float* bank, const float* lambdas
     int grid = num_cus();
     if (grid > s.ntiles) grid = s.ntiles;
     s.dbg = sn::debug_env_int("SN_CONV_LIN_DBG");   // (0 in the product: common.h)
-    s.tol = sn::option_conv_i8_tolerance();
+    s.tol = sn::conv_i8_tolerance();
     if (out_dtype == SN_BF16) s.tol = 0.0f;   // bf16 storage rounds at 2^-9: the 24-bit fixed point is not what limits it
     s.route = nullptr;
     s.prep = static_cast<const uint8_t*>(prep);
@@ -665,7 +665,7 @@ int sn::conv_fused_prep_launch(const float* bank, const float* lambdas, int G, i
     bool w24 = false;
     if (!lin_plan(1, TZ, TX, TY, G, kz, kx, ky, s, lds, w24)) return SN_ERR_UNSUPPORTED;
     s.gate = sn::current_gate();
-    s.tol = sn::option_conv_i8_tolerance();
+    s.tol = sn::conv_i8_tolerance();
     s.route = nullptr;
     s.prep = nullptr;
     s.dbg = 0;

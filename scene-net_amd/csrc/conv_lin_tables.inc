@@ -232,7 +232,7 @@ inline bool lin_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, 
     s.ntiles = (int)nt;
     s.npairs = kz * kx;
     // 24-byte packing of the kernel rows when a strip's window fits 24 halo bytes (ky <= 9 with PYA == py)
-    w24 = (s.PYA - s.py + 15 + ky - 1 < 24) && !sn::option_extra(sn::kOptConvLinNo24);
+    w24 = (s.PYA - s.py + 15 + ky - 1 < 24) && !sn::option(sn::kOptConvLinNo24);
     s.nsteps = w24 ? (3 * s.npairs + 7) / 8 : (s.npairs + 1) / 2;   // odd counts end with a lone step after the pairs
     s.XP = kLinTX + kx - 1;
     s.rows = (kLinTZ + kz - 1) * s.XP;

@@ -748,15 +748,15 @@ int sn::corr_mfma_rows(int B, int Z, int X, int Y, int kz, int kx, int ky) {
 }
 
 size_t sn::corr_sparse_ws_bytes(int x_dtype, int B, int Z, int X, int Y, int kz, int kx, int ky) {
-    if (x_dtype != SN_OCC8 || sn::option_extra(sn::kOptCorrDense)) return 0;
+    if (x_dtype != SN_OCC8 || sn::option(sn::kOptCorrDense)) return 0;
     SparsePlan p;
-    return plan_sparse(B, Z, X, Y, kz, kx, ky, sn::option_corr_sparse_tile_bytes(), &p) ? p.ws_bytes : 0;
+    return plan_sparse(B, Z, X, Y, kz, kx, ky, sn::option(sn::kOptCorrSparseTileBytes), &p) ? p.ws_bytes : 0;
 }
 
 int sn::corr_sparse_launch(const void* x, const void* gout, const void* out, int g_dtype, int B, int Z, int X, int Y, int kz,
                            int kx, int ky, void* ws, float* C, hipStream_t stream) {
     SparsePlan p;
-    if (!plan_sparse(B, Z, X, Y, kz, kx, ky, sn::option_corr_sparse_tile_bytes(), &p))
+    if (!plan_sparse(B, Z, X, Y, kz, kx, ky, sn::option(sn::kOptCorrSparseTileBytes), &p))
         return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_corr_ws: shape outside the sparse correlation kernels");
     SparseShape& s = p.s;
     s.vec = (Y % 8 == 0) && ((uintptr_t)x % 8 == 0);

@@ -1441,7 +1441,7 @@ extern "C" int sn_voxel_finalize(const int32_t* counts, const int32_t* tower_cou
 // the one-pass kernel serves grids whose bitmap(s) fit one workgroup's LDS (no z-slabs): 64^3 with or without the GT plane
 static bool onepass_eligible(int nx, int ny, int nz, int planes) {
     const size_t V = (size_t)nx * ny * nz;
-    return sn::option_voxel_onepass() && V % 32 == 0 && (V / 32) * planes <= (size_t)kMaxOccWords;
+    return sn::option(sn::kOptVoxelOnepass) && V % 32 == 0 && (V / 32) * planes <= (size_t)kMaxOccWords;
 }
 
 // sn_voxel_occupancy (descriptor given) and sn_voxel_occupancy_fused (box_parts given: the binning kernel derives the
@@ -1506,7 +1506,7 @@ static int occupancy_impl(const double* pts, const double* labels, const int64_t
             return sn::check_launch("sn_voxel_occupancy_fused(hipFuncSetAttribute)");
         hipLaunchKernelGGL(kern, dim3(kOneParts, B + rider_rows), dim3(kOneThreads), lds1, s, pts, labels, offsets, nx, ny, nz,
                            words, planes, keep, bits_ws, dropped_parts, flags, const_cast<double*>(box_parts), epoch, regular,
-                           desc, bbox_out, sn::option_voxel_onepass_spin(), rider_rows, r);
+                           desc, bbox_out, sn::option(sn::kOptVoxelOnepassSpin), rider_rows, r);
     } else {
         auto kern = al ? occ_partial_kernel<true> : occ_partial_kernel<false>;
         if (sn::ensure_dynamic_lds((const void*)kern, 96 * 1024) != hipSuccess)

@@ -304,13 +304,10 @@ def test_skip_empty_tiles_option_changes_nothing_but_time(hip_device):
                              occ_dtype=torch.bool).occ
     assert _hip.get_option("conv_skip_empty_tiles") == 0
     act0, out0 = _hip.conv_bank(occ, bank, lam, want_act=True, want_out=True)
-    _hip.set_option("conv_skip_empty_tiles", 1)
-    try:
+    with _hip.options(conv_skip_empty_tiles=1):
         act1, out1 = _hip.conv_bank(occ, bank, lam, want_act=True, want_out=True)
         empty = torch.zeros_like(occ)
         a2, o2 = _hip.conv_bank(empty, bank, lam, want_act=True, want_out=True)
-    finally:
-        _hip.set_option("conv_skip_empty_tiles", 0)
     assert torch.equal(act0, act1) and torch.equal(out0, out1)
     assert a2.abs().max().item() == 0 and o2.abs().max().item() == 0
     with pytest.raises(sna.HipLibraryError):
@@ -387,11 +384,8 @@ def test_fused_linear_row_packings_are_bit_identical(hip_device, shape, ks):
     bank = (_rand_bank(G, ks, 3, "cpu") * torch.logspace(-1, 0.3, G).view(G, 1, 1, 1)).to(hip_device).contiguous()
     lam = ((torch.rand(G) - 0.4) / G).to(hip_device)
     packed = _hip.conv_fused(x, bank, lam)
-    _hip.set_option("conv_lin_no24", 1)   # (an option now: the environment is read once, never per call)
-    try:
+    with _hip.options(conv_lin_no24=1):   # (an option now: the environment is read once, never per call)
         wide = _hip.conv_fused(x, bank, lam)
-    finally:
-        _hip.set_option("conv_lin_no24", 0)
     assert torch.equal(packed, wide)
 
 

@@ -17,17 +17,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
 
-class fold:
-    def __init__(self, on):
-        self.on = on
-
-    def __enter__(self):
-        _hip.set_option("conv_i8_fold", 1 if self.on else 0)
-
-    def __exit__(self, *a):
-        _hip.set_option("conv_i8_fold", 1)
-
-
 def _symmetric_bank(G, seed, scale=None):
     g = torch.Generator().manual_seed(seed)
     w = torch.rand((G, 9, 9, 9), generator=g) - 0.5
@@ -62,14 +51,14 @@ def test_folded_equals_unfolded_and_oracle(hip_device, shape, G):
     ref_out = torch.relu(torch.tanh((lam.double().view(1, G, 1, 1, 1) * ref_act).sum(1, keepdim=True)))
     x, b, l = occ.to(hip_device), bank.to(hip_device), lam.to(hip_device)
     c0 = _hip.conv_i8_path_counts()
-    with fold(True):
+    with _hip.options(conv_i8_fold=1):
         act_f, out_f = _run(x, b, l)
         _, only_f = _run(x, b, l, want_act=False)
         act_d, out_d = _run(x, b, l, dt=torch.float64)
     served, declined, routed = _delta(c0, _hip.conv_i8_path_counts())
     groups = (G + 15) // 16
     assert served == 3 * groups and declined == 0 and routed == 0, (served, declined, routed)
-    with fold(False):
+    with _hip.options(conv_i8_fold=0):
         act_u, out_u = _run(x, b, l)
         _, only_u = _run(x, b, l, want_act=False)
     assert _delta(c0, _hip.conv_i8_path_counts())[0] == 3 * groups   # the folded kernel was not even tried
@@ -93,11 +82,11 @@ def test_one_ulp_off_symmetry_takes_the_unfolded_kernel(hip_device):
         b[where] = torch.nextafter(v, v + 1)   # one ulp: the mirrored tap no longer matches (or it is its own mirror)
         own_mirror = where[2] == 4 and where[3] == 4
         c0 = _hip.conv_i8_path_counts()
-        with fold(True):
+        with _hip.options(conv_i8_fold=1):
             act, out = _run(x, b.to(hip_device), l)
         served, declined, routed = _delta(c0, _hip.conv_i8_path_counts())
         assert (served, declined) == ((1, 0) if own_mirror else (0, 1)), (where, served, declined)
-        with fold(False):
+        with _hip.options(conv_i8_fold=0):
             act_u, out_u = _run(x, b.to(hip_device), l)
         assert torch.equal(act, act_u) and torch.equal(out, out_u)
         ref = go.conv_bank(occ.double(), b.double().unsqueeze(1))
@@ -118,7 +107,7 @@ def test_geneo_banks_are_served_folded(hip_device):
     c0 = _hip.conv_i8_path_counts()
     act, out = _run(occ, bank, lam)
     assert _delta(c0, _hip.conv_i8_path_counts()) == (1, 0, 0)
-    with fold(False):
+    with _hip.options(conv_i8_fold=0):
         act_u, out_u = _run(occ, bank, lam)
     assert torch.equal(act, act_u) and torch.equal(out, out_u)
     ref = go.conv_bank(occ.cpu().double(), bank.cpu().double().unsqueeze(1))
@@ -159,7 +148,7 @@ def test_full_c2_batch_and_128_cubed_folded_equals_unfolded(hip_device):
         c0 = _hip.conv_i8_path_counts()
         outs = [_hip.conv_bank(x, b, l, want_act=False, want_out=True)[1] for _ in range(3)]
         assert _delta(c0, _hip.conv_i8_path_counts()) == (3, 0, 0)
-        with fold(False):
+        with _hip.options(conv_i8_fold=0):
             ref = _hip.conv_bank(x, b, l, want_act=False, want_out=True)[1]
         for o in outs:
             assert torch.equal(o, ref)
@@ -182,7 +171,7 @@ def test_random_shapes_folded_equals_unfolded(hip_device):
         act_f, out_f = _run(x, b, l)
         served, declined, routed = _delta(c0, _hip.conv_i8_path_counts())
         assert (served, declined, routed) == ((G + 15) // 16, 0, 0), (case, (B, Z, X, Y, G), served, declined, routed)
-        with fold(False):
+        with _hip.options(conv_i8_fold=0):
             act_u, out_u = _run(x, b, l)
         assert torch.equal(act_f, act_u) and torch.equal(out_f, out_u), (case, (B, Z, X, Y, G))
         ref_act = go.conv_bank(occ.double(), bank.double().unsqueeze(1))

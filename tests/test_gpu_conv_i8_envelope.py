@@ -1,5 +1,5 @@
 """The int8 kernels' parity envelope on the MI355X: K3' in both forms (stride-4 kernel
-conv_i8s.hip, four-copy kernel conv_i8.hip) and K3L (conv_lin.hip) at occupancy densities the LiDAR-shaped tests never
+conv_i8s.hip, four-copy kernel conv_i8.hip for every shape with option conv_i8_legacy = 1) and K3L (conv_lin.hip) at occupancy densities the LiDAR-shaped tests never
 reach, with banks of large weights, at 128^3 -- each against the fp64 oracle, against the ANALYTIC bound of the
 24-bit fixed-point quantisation, and with the device-side route to the fp32 kernel checked where the bound cannot
 meet the tolerance.  Tolerance (north_star): activations within 1e-4 (relative to max(1, |act|))."""
@@ -28,18 +28,6 @@ def quant_bound(w):
     S = QMAX / m
     e = np.rint(w * S) / S - w
     return float(max(e[e > 0].sum(), -e[e < 0].sum()))
-
-
-class legacy_kernel:
-    """sn_set_option("conv_i8_legacy", 1): the four-copy int8 kernel for every shape."""
-    def __init__(self, on):
-        self.on = on
-
-    def __enter__(self):
-        _hip.set_option("conv_i8_legacy", 1 if self.on else 0)
-
-    def __exit__(self, *a):
-        _hip.set_option("conv_i8_legacy", 0)
 
 
 def _bench_bank(dev, sigma_scale=1.0):
@@ -91,7 +79,7 @@ def test_bench_bank_dense_occupancy(hip_device, density, legacy):
     torch.manual_seed(int(density * 10))
     occ = torch.rand(1, 1, 24, 24, 64) < density if density < 1 else torch.ones(1, 1, 24, 24, 64, dtype=torch.bool)
     bank, lam = _bench_bank(hip_device)
-    with legacy_kernel(legacy):
+    with _hip.options(conv_i8_legacy=legacy):
         errs, bounds, routed = _check_against_oracle(occ, bank, lam, hip_device, expect_route=False,
                                                      what=f"bench bank d={density} legacy={legacy}")
     print(f"density {density} legacy {legacy}: max err {errs.max():.2e}, max bound {bounds.max():.2e}, "
@@ -107,17 +95,12 @@ def test_large_sigma_bank_routes_to_fp32(hip_device, density, legacy):
     occ = torch.rand(1, 1, 16, 16, 64) < density if density < 1 else torch.ones(1, 1, 16, 16, 64, dtype=torch.bool)
     bank, lam = _bench_bank(hip_device, sigma_scale=4.0)
     assert bank.abs().max().item() >= 4.0
-    with legacy_kernel(legacy):
+    with _hip.options(conv_i8_legacy=legacy):
         _check_against_oracle(occ, bank, lam, hip_device, expect_route=True, what=f"sigma x4 d={density}")
     # with the guard off the int8 kernels run anyway, and stay inside the analytic bound (which is above the bar)
-    old = _hip.get_option("conv_i8_tolerance_ppb")
-    _hip.set_option("conv_i8_tolerance_ppb", 0)
-    try:
-        with legacy_kernel(legacy):
-            x = occ.to(hip_device)
-            act, _ = _hip.conv_bank(x, bank.to(hip_device).contiguous(), None, want_act=True, want_out=False)
-    finally:
-        _hip.set_option("conv_i8_tolerance_ppb", old)
+    with _hip.options(conv_i8_tolerance_ppb=0, conv_i8_legacy=legacy):
+        x = occ.to(hip_device)
+        act, _ = _hip.conv_bank(x, bank.to(hip_device).contiguous(), None, want_act=True, want_out=False)
     ref_act = go.conv_bank(occ.double(), bank.double().unsqueeze(1))
     for g in range(bank.shape[0]):
         err = (act[:, g].cpu().double() - ref_act[:, g]).abs().max().item()
@@ -186,7 +169,7 @@ def test_128_cubed_tile_int8_kernels_against_oracle(hip_device):
     b, l = bank.to(hip_device).contiguous(), lam.float().to(hip_device)
     outs = {}
     for legacy in (False, True):
-        with legacy_kernel(legacy):
+        with _hip.options(conv_i8_legacy=legacy):
             act, out = _hip.conv_bank(x, b, l, want_act=True, want_out=True)
         e_act = (act.cpu().double() - ref_act).abs().max().item()
         e_out = (out.cpu().double() - ref_out).abs().max().item()
@@ -226,7 +209,7 @@ def test_stride4_kernel_shapes_against_oracle_and_legacy(hip_device, shape, ks, 
     x, b, l = occ.to(hip_device), bank.to(hip_device).contiguous(), lam.to(hip_device)
     res = {}
     for legacy in (False, True):
-        with legacy_kernel(legacy):
+        with _hip.options(conv_i8_legacy=legacy):
             for dt in (torch.float32, torch.float64):
                 act, out = _hip.conv_bank(x, b, l, want_act=True, want_out=True, out_dtype=dt)
                 assert act_err_ok(act, ref_act, TOL)
@@ -248,12 +231,12 @@ def test_stride4_kernel_full_batch_equals_legacy_bit_for_bit(hip_device):
     x = torch.rand((32, 1, 64, 64, 64), device=hip_device) < 0.035
     x[3] = True                      # one completely full tile
     x[7] = False                     # one empty tile
-    with legacy_kernel(True):
+    with _hip.options(conv_i8_legacy=1):
         a0, o0 = _hip.conv_bank(x, b, l, want_act=False, want_out=True)
     for _ in range(3):               # and again: no dependence on launch-to-launch timing of the ring
         a1, o1 = _hip.conv_bank(x, b, l, want_act=False, want_out=True)
         assert torch.equal(o0, o1)
-    with legacy_kernel(True):
+    with _hip.options(conv_i8_legacy=1):
         act0, _ = _hip.conv_bank(x[:8].contiguous(), b, l, want_act=True, want_out=False)
     act1, _ = _hip.conv_bank(x[:8].contiguous(), b, l, want_act=True, want_out=False)
     assert torch.equal(act0, act1)

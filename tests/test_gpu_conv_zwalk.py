@@ -39,10 +39,8 @@ def _symmetric_bank(G, seed, scale=None):
 @pytest.fixture(params=[0, 1, 2], ids=["2rows_8waves", "1row_12waves", "1rowx2_12waves"], autouse=True)
 def zwalk_variant(request):
     """every test runs on the three shapes of the walk's rounds (sn_set_option "conv_i8z_variant")"""
-    default = _hip.get_option("conv_i8z_variant")
-    _hip.set_option("conv_i8z_variant", request.param)
-    yield request.param
-    _hip.set_option("conv_i8z_variant", default)
+    with _hip.options(conv_i8z_variant=request.param):
+        yield request.param
 
 
 @pytest.fixture(autouse=True)
@@ -154,12 +152,9 @@ def test_zwalk_guard_routes_a_wide_bank_to_fp32(hip_device):
     a_f, o_f = _hip.conv_bank(x.view(torch.uint8), b, l, want_act=True, want_out=True)   # u8: the fp32 kernel
     assert torch.equal(a_z, a_f) and torch.equal(o_z, o_f)
     # the same blob, tolerance off: the int8 path serves it
-    _hip.set_option("conv_i8_tolerance_ppb", 0)
-    try:
+    with _hip.options(conv_i8_tolerance_ppb=0):
         a_i, o_i = _hip.conv_bank(x, b, l, want_act=True, want_out=True, prep=prep)
         a_r, o_r = _hip.conv_bank(x, b, l, want_act=True, want_out=True)
-    finally:
-        _hip.set_option("conv_i8_tolerance_ppb", 90000)
     assert torch.equal(a_i, a_r) and torch.equal(o_i, o_r)
 
 
@@ -310,16 +305,10 @@ def test_all_positive_and_zero_mean_banks_agree_in_every_int8_kernel(hip_device)
         ref_out = torch.relu(torch.tanh((lam.double().view(1, 16, 1, 1, 1) * ref_act).sum(1, keepdim=True)))
         outs = {"zwalk": _hip.conv_bank(x, b, l, want_act=True, want_out=True, prep=prep)}
         outs["folded"] = _hip.conv_bank(x, b, l, want_act=True, want_out=True)
-        _hip.set_option("conv_i8_fold", 0)
-        try:
+        with _hip.options(conv_i8_fold=0):
             outs["stride-4"] = _hip.conv_bank(x, b, l, want_act=True, want_out=True)
-        finally:
-            _hip.set_option("conv_i8_fold", 1)
-        _hip.set_option("conv_i8_legacy", 1)
-        try:
+        with _hip.options(conv_i8_legacy=1):
             outs["four-copy"] = _hip.conv_bank(x, b, l, want_act=True, want_out=True)
-        finally:
-            _hip.set_option("conv_i8_legacy", 0)
         a0, o0 = outs["zwalk"]
         for k, (a, o) in outs.items():
             assert torch.equal(a, a0) and torch.equal(o, o0), (name, k)
@@ -396,16 +385,13 @@ def test_fused_forward_learns_its_verdict_and_drops_the_gated_launches(hip_devic
         verdict = model._fused_state["verdict"]   # (a fresh state: new blob, new verdict)
         word = _hip.conv_fused_prep_verdict(model._fused_state["blob"], (9, 9, 9))
         # an impossible tolerance: verdict 1, never "served", the fp32 contraction's result
-        _hip.set_option("conv_i8_tolerance_ppb", 1)
-        try:
+        with _hip.options(conv_i8_tolerance_ppb=1):
             strict = model(x)
             torch.cuda.synchronize()
             assert int(word.item()) == 1
             assert torch.equal(model(x), strict) and verdict._state == 3
             bank, lam = model.compute_bank(hip_device), model.effective_lambdas(hip_device)
             assert torch.equal(strict, _hip.conv_bank(x.view(torch.uint8), bank, lam, want_act=False, want_out=True)[1])
-        finally:
-            _hip.set_option("conv_i8_tolerance_ppb", 90000)
 
 
 @pytest.mark.parametrize("ks", [(9, 9, 9), (9, 5, 5), (6, 5, 6), (9, 7, 7)])
@@ -426,16 +412,13 @@ def test_fused_forward_on_prepared_tables(hip_device, ks):
             assert torch.equal(want, got), (ks, shape, dt)
     torch.cuda.synchronize()
     assert int(_hip.conv_fused_prep_verdict(blob, ks).item()) == 0
-    _hip.set_option("conv_i8_tolerance_ppb", 1)
-    try:
+    with _hip.options(conv_i8_tolerance_ppb=1):
         strict = _hip.conv_fused_prep(bank, lam)
         x = torch.rand(2, 1, 16, 16, 64, device=hip_device) < 0.06
         got = _hip.conv_fused(x, bank, lam, prep=strict)
         torch.cuda.synchronize()
         assert int(_hip.conv_fused_prep_verdict(strict, ks).item()) == 1
         assert torch.equal(got, _hip.conv_bank(x.view(torch.uint8), bank, lam, want_act=False, want_out=True)[1])
-    finally:
-        _hip.set_option("conv_i8_tolerance_ppb", 90000)
 
 
 # ---------------------------------------------------------------------------------------------- round 4: loud, not quiet
@@ -462,12 +445,9 @@ def test_spin_give_up_is_loud(hip_device):
     good_a, good_o = _hip.conv_bank(occ, bank, lam, want_act=True, want_out=True, prep=prep)
     t0 = _hip.conv_i8_spin_timeouts()
     assert _hip.device_status()[0] == 0
-    _hip.set_option("conv_i8z_inject_fault", 1)
-    try:
+    with _hip.options(conv_i8z_inject_fault=1):
         # (the call itself returns: the kernel is asynchronous and nothing was latched when it was enqueued)
         act, out = _hip.conv_bank(occ, bank, lam, want_act=True, want_out=True, prep=prep)
-    finally:
-        _hip.set_option("conv_i8z_inject_fault", 0)
     torch.cuda.synchronize()
     assert bool(torch.isnan(out).all()) and bool(torch.isnan(act).all())
     _expect_latched(1)
@@ -511,8 +491,7 @@ def test_fused_forward_assumed_served_on_a_declined_bank_is_loud(hip_device):
     x = (torch.rand(2, 1, 32, 32, 64, device=hip_device) < 0.05)
     bank, lam = model.compute_bank(hip_device), model.effective_lambdas(hip_device)
     blob = torch.empty(_hip.conv_fused_prep_bytes((9, 9, 9)), dtype=torch.uint8, device=hip_device)
-    _hip.set_option("conv_i8_tolerance_ppb", 1)      # a tolerance nothing meets: the blob's verdict is 1
-    try:
+    with _hip.options(conv_i8_tolerance_ppb=1):      # a tolerance nothing meets: the blob's verdict is 1
         _hip.conv_fused_prep(bank, lam, blob)
         out = _hip.conv_fused(x, bank, lam, out_dtype=torch.float32, prep=blob, assume_served=True)
         torch.cuda.synchronize()
@@ -520,8 +499,6 @@ def test_fused_forward_assumed_served_on_a_declined_bank_is_loud(hip_device):
         _expect_latched(2)
         kept = _hip.conv_fused(x, bank, lam, out_dtype=torch.float32, prep=blob, assume_served=False)
         assert torch.equal(kept, _hip.conv_bank(x.view(torch.uint8), bank, lam, want_act=False, want_out=True)[1])
-    finally:
-        _hip.set_option("conv_i8_tolerance_ppb", 90000)
     assert _hip.device_status()[0] == 0
 
 

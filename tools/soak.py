@@ -61,9 +61,6 @@ run("headline step (K1 + riders, K3'z)", headline)
 assert _hip.conv_i8_spin_timeouts() == 0 and _hip.device_status()[0] == 0
 run("contraction (K3')", contraction)
 run("linear (K3L)", linear)
-_hip.set_option("conv_skip_empty_tiles", 1)
-try:
+with _hip.options(conv_skip_empty_tiles=1):
     run("contraction, skip-empty", contraction)
-finally:
-    _hip.set_option("conv_skip_empty_tiles", 0)
 print("soak ok")
