@@ -588,6 +588,31 @@ int sn_criterion_backward(const void* pred, int pred_dtype, const void* gt, int 
 int sn_binary_stats(const void* pred, int pred_dtype, const void* target, int target_dtype, int64_t n, double tau,
                     double beta, void* parts_ws, uint64_t* state, uint64_t* batch, float* values, sn_stream_t stream);
 
+/* K6 at T thresholds in one pass: the precision-recall curve's counts.
+ * replaces: the BinnedAveragePrecision(num_classes=1, thresholds=torch.linspace(0.5, 0.95, 20)) that the reference's
+ *           MetricCollection carries commented out (utils/scripts_utils.py:90), and T calls of sn_binary_stats.
+ *
+ * pred / target hold S equal segments of n elements each (S = 1: the whole batch; S = B, n = Z*X*Y: one curve per
+ * tile); dtypes and the element-alignment rule are sn_binary_stats'.  thresholds_host [T] fp64, HOST memory, read during
+ * the call only (they travel as kernel arguments: a captured replay keeps those of capture time), strictly increasing,
+ * inside (0, 1), 1 <= T <= SN_CURVE_MAX_THRESHOLDS.  Each is rounded to pred's dtype the way sn_binary_stats rounds tau;
+ * two that round to the same value are legal and give equal columns.
+ * Per segment, bin(p) = number of rounded thresholds <= p, in 0..T (NaN: 0), and a record of
+ * SN_CURVE_RECORD(T) = 2 * (T + 1) + 2 u64:  hist[2][T + 1] (target negative, then positive), bad_pred, bad_target.
+ * For every k the counts sn_binary_stats gives for that segment at tau = thresholds[k] are
+ *   tp = sum_{b > k} hist[1][b], fp = sum_{b > k} hist[0][b], fn = sum hist[1] - tp, tn = sum hist[0] - fp,
+ * and bad_pred / bad_target are its counters (they do not depend on the threshold).
+ * state [S][SN_CURVE_RECORD(T)] u64: caller-owned, ACCUMULATES this call's records; batch (nullable, same shape): this
+ * call's records.  parts_ws: scratch of ws_bytes >= sn_binary_curve_ws_bytes(n, S, T) (0 for a shape the entry refuses),
+ * 8-byte aligned.  S <= 2^20, S * n <= 2^40.  Two launches (histogram pass, combine), LDS integer adds inside a workgroup
+ * only, plain stores, no allocation, no synchronisation: capturable, and independent of launch order. */
+#define SN_CURVE_MAX_THRESHOLDS 255
+#define SN_CURVE_RECORD(T) (2 * ((T) + 1) + 2)
+size_t sn_binary_curve_ws_bytes(int64_t n, int S, int T);
+int sn_binary_curve(const void* pred, int pred_dtype, const void* target, int target_dtype, int64_t n, int S,
+                    const double* thresholds_host, int T, void* parts_ws, size_t ws_bytes, uint64_t* state,
+                    uint64_t* batch, sn_stream_t stream);
+
 
 #ifdef __cplusplus
 }

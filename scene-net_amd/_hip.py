@@ -91,6 +91,8 @@ SYMBOLS = {
                              + [_P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
     "sn_criterion_backward": (c_int, [_P, _I, _P, _I, _I, ctypes.c_int64, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
     "sn_binary_stats": (c_int, [_P, _I, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
+    "sn_binary_curve_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I, _I]),
+    "sn_binary_curve": (c_int, [_P, _I, _P, _I, ctypes.c_int64, _I, _P, _I, _P, ctypes.c_size_t, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -99,6 +101,7 @@ SN_OCC_PARTS = 16
 SN_BBOX_PARTS = 32
 SN_METRIC_NCOUNT, SN_METRIC_NVALUE, SN_METRIC_MAX_PARTS = 6, 5, 1024
 SN_METRIC_WS_BYTES = SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8
+SN_CURVE_MAX_THRESHOLDS = 255
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1044,3 +1047,47 @@ def binary_stats(pred: torch.Tensor, target: torch.Tensor, tau: float, beta: flo
                                 _ptr(state, torch.int64, "state"), _ptr(batch, torch.int64, "batch"),
                                 _ptr(values, torch.float32, "values"), _stream())
     _check(rc, "sn_binary_stats")
+
+
+def curve_record(T: int) -> int:
+    """SN_CURVE_RECORD(T): int64 words of one segment's record -- hist[2][T + 1], bad_pred, bad_target."""
+    return 2 * (int(T) + 1) + 2
+
+
+def curve_ws_bytes(n: int, segments: int, T: int) -> int:
+    """sn_binary_curve_ws_bytes: scratch bytes of one binary_curve call over `segments` x `n` elements (host only)."""
+    need = int(load().sn_binary_curve_ws_bytes(int(n), int(segments), int(T)))
+    if need == 0:
+        raise HipLibraryError(f"sn_binary_curve serves no call of {segments} segment(s) x {n} elements at {T} thresholds "
+                              f"(n > 0, 1 <= segments <= 2^20, segments * n <= 2^40, 1 <= T <= {SN_CURVE_MAX_THRESHOLDS})")
+    return need
+
+
+@_on_tensor_device
+def binary_curve(pred: torch.Tensor, target: torch.Tensor, thresholds, ws: torch.Tensor, state: torch.Tensor,
+                 segments: int = 1, batch: Optional[torch.Tensor] = None) -> None:
+    """sn_binary_curve over pred / target flattened (same numel, `segments` equal parts): adds each segment's record --
+    hist[2][T + 1] (bin = number of thresholds the prediction clears; target negative, then positive), bad_pred,
+    bad_target -- to `state` [segments, curve_record(T)] int64; `batch` (optional, same shape) receives this call's.
+    thresholds: T floats, or a ctypes array of c_double built once.  ws: scratch of curve_ws_bytes(n, segments, T).
+    Two launches on the current stream, no synchronisation."""
+    if pred.numel() != target.numel():
+        raise ValueError(f"pred ({pred.numel()} elements) and target ({target.numel()} elements) must have the same size")
+    segments = int(segments)
+    if segments < 1 or pred.numel() % segments:
+        raise ValueError(f"{pred.numel()} elements do not split into {segments} equal segments")
+    if pred.dtype not in _METRIC_PRED_DT:
+        raise HipLibraryError(f"pred must be float32, bfloat16 or float64 (got {pred.dtype})")
+    if target.dtype not in _METRIC_TGT_DT:
+        raise HipLibraryError(f"target must be float32, float64, bfloat16, uint8, bool or int32 (got {target.dtype})")
+    thr = thresholds if isinstance(thresholds, ctypes.Array) else (ctypes.c_double * len(thresholds))(
+        *[float(v) for v in thresholds])
+    T = len(thr)
+    words = segments * curve_record(T)
+    if state.numel() != words or (batch is not None and batch.numel() != words):
+        raise HipLibraryError(f"state / batch must hold {segments} x {curve_record(T)} int64 words")
+    rc = load().sn_binary_curve(_ptr(pred, None, "pred"), _METRIC_PRED_DT[pred.dtype], _ptr(target, None, "target"),
+                                _METRIC_TGT_DT[target.dtype], pred.numel() // segments, segments, thr, T,
+                                _ptr(ws, None, "ws"), ws.numel() * ws.element_size(), _ptr(state, torch.int64, "state"),
+                                _ptr(batch, torch.int64, "batch"), _stream())
+    _check(rc, "sn_binary_curve")

@@ -5,6 +5,7 @@
 // turns counts into values.  Integer counts: exact and independent of order, no atomics.
 //
 // Bound: HBM.  Algorithmic bytes per element: sizeof(pred) + sizeof(target), read once.
+// Below it, sn_binary_curve: the same counts at T thresholds from one pass (a histogram over the thresholds cleared).
 #include "common.h"
 #include <type_traits>
 
@@ -277,4 +278,305 @@ extern "C" int sn_binary_stats(const void* pred, int pred_dtype, const void* tar
     hipLaunchKernelGGL(metrics_combine_kernel, dim3(1), dim3(kCombineThreads), 0, s, parts, nparts, n, beta, state, batch,
                        values);
     return sn::check_launch("sn_binary_stats(combine)");
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// K6 curve -- the same counting at T thresholds in ONE pass (sn_binary_curve).  Every prediction is binned by the number
+// of (rounded) thresholds it clears, split by target class; the confusion counts at threshold k are suffix sums of that
+// histogram, formed on the host.  The two end bins -- below the first threshold (relu zeros: most of a real batch) and
+// at or above the last (a saturated tanh) -- are counted in registers, a wave at a time (lane masks and population
+// counts); only what lies between goes through a branch-free binary search over an LDS table and an LDS integer add into
+// the wave's own copy of the histogram, so the cell that holds most of a real batch is never an LDS address.
+// Per-workgroup partial histograms leave as u32 with plain stores; a second launch sums them and adds into the caller's
+// u64 state.  A workgroup never straddles two segments.
+//
+// Bound: HBM by bytes (the same bytes as sn_binary_stats, read once); measured, the search's vector instructions and
+// LDS round trips keep the pass at 0.38 of the copy rate at T = 20.
+namespace {
+
+constexpr int kCurveBins = 256;                 // LDS bins per class: T + 1 <= 256
+constexpr int kCurveRows = 64, kCurveCells = 4;   // combine: 4 cells x 64 rows of partial records per workgroup
+constexpr int kMaxSegments = 1 << 20;
+static_assert(SN_CURVE_MAX_THRESHOLDS < kCurveBins && kThreads == kCurveBins, "one table slot per thread");
+
+template <typename C>
+struct CurveThresholds {
+    C v[SN_CURVE_MAX_THRESHOLDS];
+};
+
+struct CurveRegs {
+    uint32_t lo_all, lo_pos, hi_all, hi_pos, bad_pred, bad_tgt;
+};
+
+// N elements of one lane.  The end bins and the bad values are counted across the wave (a comparison leaves its lane mask
+// in scalar registers; the population counts run on the scalar unit): every counter holds the WAVE's total in each lane
+// that is still active, and lane 0 -- which holds the lowest index of its wave and so leaves every loop last -- reports
+// it.  thr[0 .. 2^STEPS) is the table padded with +Inf; hist is this wave's [2][kCurveBins] copy.  STEPS = 0 (T = 1):
+// the two end bins are all there is.
+template <int N, int STEPS, typename PT, typename TT>
+__device__ __forceinline__ void bin_elems(const PT* pv, const TT* tv, typename PredOf<PT>::type t_first,
+                                          typename PredOf<PT>::type t_last, const typename PredOf<PT>::type* thr,
+                                          uint32_t* hist, CurveRegs& c) {
+    using C = typename PredOf<PT>::type;
+    C p[N];
+    bool tt[N], mid[N], any = false;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        p[j] = (C)pv[j];
+        bool bt;
+        classify_target(tv[j], tt[j], bt);
+        const bool lo = !(p[j] >= t_first), hi = p[j] >= t_last;   // NaN clears no threshold: bin 0
+        const unsigned long long m_tt = __ballot(tt[j]), m_lo = __ballot(lo), m_hi = __ballot(hi);
+        c.lo_all += __popcll(m_lo);
+        c.lo_pos += __popcll(m_lo & m_tt);
+        c.hi_all += __popcll(m_hi);
+        c.hi_pos += __popcll(m_hi & m_tt);
+        c.bad_pred += __popcll(__ballot((p[j] < (C)0) || (p[j] > (C)1)));
+        c.bad_tgt += __popcll(__ballot(bt));
+        mid[j] = !lo && !hi;
+        any |= mid[j];
+    }
+    if constexpr (STEPS > 0) {
+        if (!__any(any)) return;
+        // bin = number of thresholds <= p; every lane searches (indices stay below 2^STEPS <= kCurveBins), mid lanes add
+        int b[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) b[j] = 0;
+#pragma unroll
+        for (int s = STEPS - 1; s >= 0; --s)
+#pragma unroll
+            for (int j = 0; j < N; ++j) b[j] += thr[b[j] + (1 << s) - 1] <= p[j] ? (1 << s) : 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (mid[j]) atomicAdd(&hist[(int)tt[j] * kCurveBins + b[j]], 1u);
+    }
+}
+
+// Partial record of workgroup w = (segment, part): parts[w * L + {cls * (T + 1) + bin | 2 * (T + 1) + {0: bad_pred,
+// 1: bad_tgt}}], L = 2 * (T + 1) + 2, u32 (a workgroup counts fewer than 2^32 elements).  The split of a segment into
+// head / aligned middle / tail is sn_binary_stats' own, taken per segment on the device (a segment of odd length
+// starts wherever it starts).
+template <int STEPS, typename PT, typename TT>
+__global__ __launch_bounds__(kThreads) void curve_hist_kernel(const PT* __restrict__ pred, const TT* __restrict__ tgt,
+                                                              int64_t n, int pps, int T,
+                                                              CurveThresholds<typename PredOf<PT>::type> th,
+                                                              uint32_t* __restrict__ parts) {
+    using C = typename PredOf<PT>::type;
+    __shared__ uint32_t hist[kThreads / 64][2][kCurveBins];
+    __shared__ C thr[kCurveBins];
+    __shared__ uint32_t wsum[kThreads / 64][6];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int seg = blockIdx.x / pps, part = blockIdx.x - seg * pps;
+    for (int i = tid; i < (kThreads / 64) * 2 * kCurveBins; i += kThreads) (&hist[0][0][0])[i] = 0u;
+    thr[tid] = tid < T ? th.v[tid] : (C)__builtin_inf();
+    __syncthreads();
+    const C t_first = thr[0], t_last = thr[T - 1];
+
+    pred += (int64_t)seg * n;
+    tgt += (int64_t)seg * n;
+    const uintptr_t pa = (uintptr_t)pred, ta = (uintptr_t)tgt;
+    int64_t head = n;
+    for (int64_t h = 0; h < 64 && h < n; ++h)
+        if ((pa + h * sizeof(PT)) % vec_align<PT>() == 0 && (ta + h * sizeof(TT)) % vec_align<TT>() == 0) {
+            head = h;
+            break;
+        }
+    const int64_t nvec = (n - head) / kElems;
+
+    CurveRegs c{0, 0, 0, 0, 0, 0};
+    uint32_t* hw = &hist[wave][0][0];
+    const int64_t gtid = (int64_t)part * kThreads + tid, gstride = (int64_t)pps * kThreads;
+    const PT* p = pred + head;
+    const TT* t = tgt + head;
+    // two chunks in flight per lane, then one, while the WHOLE wave has them (the wave's last lane decides, so that lane 0
+    // takes part in every step its wave takes); what is left is one ragged step of the wave's leading lanes
+    const int64_t wlast = (int64_t)part * kThreads + __builtin_amdgcn_readfirstlane(wave) * 64 + 63;
+    int64_t v = gtid, vl = wlast;
+    for (; vl + gstride < nvec; v += 2 * gstride, vl += 2 * gstride) {
+        const Chunk<PT> pa2 = load_chunk(p + v * kElems), pb = load_chunk(p + (v + gstride) * kElems);
+        const Chunk<TT> ta2 = load_chunk(t + v * kElems), tb = load_chunk(t + (v + gstride) * kElems);
+        bin_elems<kElems, STEPS, PT, TT>(pa2.v, ta2.v, t_first, t_last, thr, hw, c);
+        bin_elems<kElems, STEPS, PT, TT>(pb.v, tb.v, t_first, t_last, thr, hw, c);
+    }
+    if (vl < nvec) {
+        const Chunk<PT> pa2 = load_chunk(p + v * kElems);
+        const Chunk<TT> ta2 = load_chunk(t + v * kElems);
+        bin_elems<kElems, STEPS, PT, TT>(pa2.v, ta2.v, t_first, t_last, thr, hw, c);
+        v += gstride;
+    }
+    if (v < nvec) {
+        const Chunk<PT> pa2 = load_chunk(p + v * kElems);
+        const Chunk<TT> ta2 = load_chunk(t + v * kElems);
+        bin_elems<kElems, STEPS, PT, TT>(pa2.v, ta2.v, t_first, t_last, thr, hw, c);
+    }
+    for (int64_t i = gtid; i < head; i += gstride)
+        bin_elems<1, STEPS, PT, TT>(pred + i, tgt + i, t_first, t_last, thr, hw, c);
+    for (int64_t i = head + nvec * kElems + gtid; i < n; i += gstride)
+        bin_elems<1, STEPS, PT, TT>(pred + i, tgt + i, t_first, t_last, thr, hw, c);
+
+    const uint32_t w[6] = {c.lo_all, c.lo_pos, c.hi_all, c.hi_pos, c.bad_pred, c.bad_tgt};   // lane 0: the wave's totals
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) wsum[wave][k] = w[k];
+    __syncthreads();   // the waves' LDS adds have landed too
+    const int nb = T + 1, L = 2 * nb + 2;
+    uint32_t* rec = parts + (size_t)blockIdx.x * L;
+    for (int cell = tid; cell < L; cell += kThreads) {
+        uint32_t s = 0;
+        if (cell >= 2 * nb) {
+            for (int q = 0; q < kThreads / 64; ++q) s += wsum[q][4 + cell - 2 * nb];
+        } else {
+            const int cls = cell >= nb, b = cell - cls * nb;
+            if (b == 0 || b == T) {   // the register-counted end bins (T == 1: these are all there is)
+                const int k = b == 0 ? 0 : 2;
+                uint32_t all = 0, pos = 0;
+                for (int q = 0; q < kThreads / 64; ++q) all += wsum[q][k], pos += wsum[q][k + 1];
+                s = cls ? pos : all - pos;
+            } else {
+                for (int q = 0; q < kThreads / 64; ++q) s += hist[q][cls][b];
+            }
+        }
+        rec[cell] = s;
+    }
+}
+
+// state[seg * L + cell] += sum over the segment's parts; batch (nullable) receives the sum itself.  A workgroup takes
+// kCurveCells cells of one segment: kCurveRows threads per cell, each with its loads in flight eight at a time.
+__global__ __launch_bounds__(kCurveRows * kCurveCells) void curve_combine_kernel(const uint32_t* __restrict__ parts,
+                                                                                int pps, int L, int blocks_per_seg,
+                                                                                uint64_t* __restrict__ state,
+                                                                                uint64_t* __restrict__ batch) {
+    __shared__ uint64_t sh[kCurveRows][kCurveCells];
+    const int tid = threadIdx.x, col = tid % kCurveCells, row = tid / kCurveCells;
+    const int seg = blockIdx.x / blocks_per_seg;
+    const int cell = (blockIdx.x - seg * blocks_per_seg) * kCurveCells + col;
+    uint64_t s = 0;
+    if (cell < L) {
+        const uint32_t* src = parts + (size_t)seg * pps * L + cell;
+        for (int q = row; q < pps; q += 8 * kCurveRows) {
+            uint32_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = q + u * kCurveRows < pps ? src[(size_t)(q + u * kCurveRows) * L] : 0u;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += v[u];
+        }
+    }
+    sh[row][col] = s;
+    __syncthreads();
+    for (int h = kCurveRows / 2; h > 0; h >>= 1) {
+        if (row < h) sh[row][col] += sh[row + h][col];
+        __syncthreads();
+    }
+    if (row != 0 || cell >= L) return;
+    const size_t at = (size_t)seg * L + cell;
+    state[at] += sh[0][col];
+    if (batch) batch[at] = sh[0][col];
+}
+
+// workgroups per segment: two chunks per lane at least, SN_METRIC_MAX_PARTS workgroups over all segments at most
+int curve_parts_per_segment(int64_t n, int S) {
+    const int64_t want = (n + 2 * kChunk - 1) / (2 * kChunk);
+    const int64_t cap = SN_METRIC_MAX_PARTS / S > 0 ? SN_METRIC_MAX_PARTS / S : 1;
+    return (int)(want < cap ? want : cap);
+}
+
+int curve_dtype_error(const char* what, int dt) {
+    return sn::fail(dt >= SN_F32 && dt <= SN_I32 ? SN_ERR_UNSUPPORTED : SN_ERR_INVALID_ARG,
+                    "sn_binary_curve: %s dtype %d not accepted (pred: SN_F32 | SN_BF16 | SN_F64; target: SN_F32 | SN_F64 | "
+                    "SN_BF16 | SN_U8 | SN_OCC8 | SN_I32)", what, dt);
+}
+
+bool curve_shape_ok(int64_t n, int S, int T) {
+    return n > 0 && S > 0 && S <= kMaxSegments && T >= 1 && T <= SN_CURVE_MAX_THRESHOLDS && n <= kMaxN / S;
+}
+
+template <typename PT, typename TT>
+void launch_curve(const void* pred, const void* tgt, int64_t n, int S, const double* thr_host, int T, int pps,
+                  uint32_t* parts, hipStream_t s) {
+    using C = typename PredOf<PT>::type;
+    CurveThresholds<C> th;
+    for (int k = 0; k < SN_CURVE_MAX_THRESHOLDS; ++k) {
+        const double tau = k < T ? thr_host[k] : 2.0;
+        if constexpr (std::is_same<PT, bf16>::value) th.v[k] = round_bf16(tau);
+        else th.v[k] = (C)tau;
+    }
+    // steps of the search over a table of 2^steps > T slots: none at T = 1, 5 up to T = 31, 8 up to the cap
+    const dim3 grid((unsigned)(S * pps)), block(kThreads);
+    if (T == 1)
+        hipLaunchKernelGGL((curve_hist_kernel<0, PT, TT>), grid, block, 0, s, (const PT*)pred, (const TT*)tgt, n, pps, T, th,
+                           parts);
+    else if (T < 32)
+        hipLaunchKernelGGL((curve_hist_kernel<5, PT, TT>), grid, block, 0, s, (const PT*)pred, (const TT*)tgt, n, pps, T, th,
+                           parts);
+    else
+        hipLaunchKernelGGL((curve_hist_kernel<8, PT, TT>), grid, block, 0, s, (const PT*)pred, (const TT*)tgt, n, pps, T, th,
+                           parts);
+}
+
+template <typename PT>
+int dispatch_curve_target(const void* pred, const void* tgt, int tgt_dtype, int64_t n, int S, const double* thr_host,
+                          int T, int pps, uint32_t* parts, hipStream_t s) {
+    switch (tgt_dtype) {
+        case SN_F32: launch_curve<PT, float>(pred, tgt, n, S, thr_host, T, pps, parts, s); break;
+        case SN_F64: launch_curve<PT, double>(pred, tgt, n, S, thr_host, T, pps, parts, s); break;
+        case SN_BF16: launch_curve<PT, bf16>(pred, tgt, n, S, thr_host, T, pps, parts, s); break;
+        case SN_U8:
+        case SN_OCC8: launch_curve<PT, uint8_t>(pred, tgt, n, S, thr_host, T, pps, parts, s); break;
+        default: launch_curve<PT, int32_t>(pred, tgt, n, S, thr_host, T, pps, parts, s); break;
+    }
+    return SN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t sn_binary_curve_ws_bytes(int64_t n, int S, int T) {
+    if (!curve_shape_ok(n, S, T)) return 0;
+    return (size_t)S * curve_parts_per_segment(n, S) * (2 * (T + 1) + 2) * sizeof(uint32_t);
+}
+
+extern "C" int sn_binary_curve(const void* pred, int pred_dtype, const void* target, int target_dtype, int64_t n, int S,
+                               const double* thresholds_host, int T, void* parts_ws, size_t ws_bytes, uint64_t* state,
+                               uint64_t* batch, sn_stream_t stream) {
+    if (!pred || !target || !thresholds_host || !parts_ws || !state)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: null pointer");
+    if (n <= 0) return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: n must be positive");
+    if (S <= 0) return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: S must be positive");
+    if (T < 1 || T > SN_CURVE_MAX_THRESHOLDS)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: T must lie in [1, %d] (got %d)", SN_CURVE_MAX_THRESHOLDS, T);
+    if (!curve_shape_ok(n, S, T)) return sn::fail(SN_ERR_UNSUPPORTED, "sn_binary_curve: S <= 2^20 and S * n <= 2^40");
+    for (int k = 0; k < T; ++k) {
+        if (!(thresholds_host[k] > 0.0 && thresholds_host[k] < 1.0))
+            return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: thresholds must lie in (0, 1) (entry %d)", k);
+        if (k > 0 && !(thresholds_host[k] > thresholds_host[k - 1]))
+            return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: thresholds must be strictly increasing (entry %d)", k);
+    }
+    if (pred_dtype != SN_F32 && pred_dtype != SN_BF16 && pred_dtype != SN_F64) return curve_dtype_error("pred", pred_dtype);
+    if (target_dtype != SN_F32 && target_dtype != SN_F64 && target_dtype != SN_BF16 && target_dtype != SN_U8 &&
+        target_dtype != SN_OCC8 && target_dtype != SN_I32)
+        return curve_dtype_error("target", target_dtype);
+    const size_t psz = pred_dtype == SN_F64 ? 8 : (pred_dtype == SN_F32 ? 4 : 2);
+    const size_t tsz = (target_dtype == SN_F64) ? 8 : (target_dtype == SN_U8 || target_dtype == SN_OCC8) ? 1
+                       : (target_dtype == SN_BF16) ? 2 : 4;
+    if ((uintptr_t)pred % psz || (uintptr_t)target % tsz)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: pred / target must be aligned to their element size");
+    if ((uintptr_t)parts_ws % 8 || (uintptr_t)state % 8 || (uintptr_t)batch % 8)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: parts_ws / state / batch must be 8-byte aligned");
+    const size_t need = sn_binary_curve_ws_bytes(n, S, T);
+    if (ws_bytes < need)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_binary_curve: parts_ws holds %zu bytes, %zu needed "
+                        "(sn_binary_curve_ws_bytes)", ws_bytes, need);
+    hipStream_t s = sn::as_stream(stream);
+    const int pps = curve_parts_per_segment(n, S);
+    uint32_t* parts = static_cast<uint32_t*>(parts_ws);
+    switch (pred_dtype) {
+        case SN_F32: dispatch_curve_target<float>(pred, target, target_dtype, n, S, thresholds_host, T, pps, parts, s); break;
+        case SN_BF16: dispatch_curve_target<bf16>(pred, target, target_dtype, n, S, thresholds_host, T, pps, parts, s); break;
+        default: dispatch_curve_target<double>(pred, target, target_dtype, n, S, thresholds_host, T, pps, parts, s); break;
+    }
+    if (int e = sn::check_launch("sn_binary_curve(histogram)")) return e;
+    const int L = 2 * (T + 1) + 2, blocks_per_seg = (L + kCurveCells - 1) / kCurveCells;
+    hipLaunchKernelGGL(curve_combine_kernel, dim3((unsigned)(S * blocks_per_seg)), dim3(kCurveRows * kCurveCells), 0, s,
+                       parts, pps, L, blocks_per_seg, state, batch);
+    return sn::check_launch("sn_binary_curve(combine)");
 }

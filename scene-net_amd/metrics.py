@@ -21,11 +21,15 @@ dependency of this package and was not available to check against, so the readin
     background too).
 Unlike torchmetrics, a bad pred or target does not raise in update(): the kernel counts them and compute() raises
 ValueError (an update must not synchronise).  There is no CPU path: CPU tensors raise HipLibraryError.
+
+BinarySegmentationCurve (below) is the same collection at T thresholds from ONE pass (sn_binary_curve): the
+precision-recall curve, the binned average precision and the best threshold.
 """
 from __future__ import annotations
 
+import ctypes
 import warnings
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -176,3 +180,207 @@ class _MetricView:
 def init_metrics(tau: float = 0.65) -> BinarySegmentationMetrics:
     """utils/scripts_utils.py:init_metrics: the drop-in `metric_initializer` of LitSceneNet."""
     return BinarySegmentationMetrics(tau=tau, beta=0.5)
+
+
+# --------------------------------------------------------------------------- #
+# The threshold sweep: the counts of T thresholds from one pass (sn_binary_curve).
+CURVE_COUNT_NAMES = ("tp", "fp", "fn", "tn")
+
+
+def _check_thresholds(thresholds) -> Tuple[float, ...]:
+    """The C entry's own rules: 1 <= T <= SN_CURVE_MAX_THRESHOLDS, strictly increasing, inside (0, 1)."""
+    thr = tuple(float(v) for v in (thresholds.tolist() if isinstance(thresholds, torch.Tensor) else thresholds))
+    if not 1 <= len(thr) <= _hip.SN_CURVE_MAX_THRESHOLDS:
+        raise ValueError(f"between 1 and {_hip.SN_CURVE_MAX_THRESHOLDS} thresholds are served (got {len(thr)})")
+    for k, v in enumerate(thr):
+        if not 0.0 < v < 1.0:
+            raise ValueError(f"thresholds must lie in (0, 1) (entry {k} is {v})")
+        if k and not v > thr[k - 1]:
+            raise ValueError(f"thresholds must be strictly increasing (entry {k}: {v} after {thr[k - 1]})")
+    return thr
+
+
+def curve_counts(hist: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """hist [..., 2, T + 1] int64 (bin = number of thresholds a prediction clears; target negative, then positive) ->
+    {"tp", "fp", "fn", "tn"} int64 [..., T]: at threshold k the predicted positives are the bins above k."""
+    hist = hist.to(torch.int64)
+    above = hist.flip(-1).cumsum(-1).flip(-1)[..., 1:]      # [..., 2, T]: sum over bins b > k
+    total = hist.sum(-1, keepdim=True)
+    fp, tp = above[..., 0, :], above[..., 1, :]
+    return {"tp": tp, "fp": fp, "fn": total[..., 1, :] - tp, "tn": total[..., 0, :] - fp}
+
+
+def curve_values(tp, fp, fn, tn, beta: float = 0.5) -> Dict[str, torch.Tensor]:
+    """The five values per threshold, fp32 [..., T]: every entry is binary_metric_values of its column."""
+    shape = tp.shape
+    cols = [binary_metric_values(a, b, c, d, beta) for a, b, c, d in
+            zip(tp.reshape(-1).tolist(), fp.reshape(-1).tolist(), fn.reshape(-1).tolist(), tn.reshape(-1).tolist())]
+    return {n: torch.tensor([c[n] for c in cols], dtype=torch.float32).reshape(shape) for n in METRIC_NAMES}
+
+
+def binned_average_precision(tp: Sequence[int], fp: Sequence[int], fn: Sequence[int]) -> float:
+    """torchmetrics 0.9's BinnedAveragePrecision as we read it (unpinned: torchmetrics was not available to check
+    against): with P_k, R_k the fp64 precision and recall at threshold k (0/0 -> 0) and (P, R) = (1, 0) appended after
+    the last threshold, AP = -sum_k (R_{k+1} - R_k) P_k, summed in threshold order in fp64 and rounded once to fp32."""
+    P = [_ratio(float(a), float(a) + float(b)) for a, b in zip(tp, fp)] + [1.0]
+    R = [_ratio(float(a), float(a) + float(c)) for a, c in zip(tp, fn)] + [0.0]
+    ap = 0.0
+    for k in range(len(P) - 1):
+        ap -= (R[k + 1] - R[k]) * P[k]
+    return float(torch.tensor(ap, dtype=torch.float32))
+
+
+def best_index(values: Sequence[float]) -> int:
+    """Index of the largest value; ties go to the lowest index (the lowest threshold)."""
+    best = 0
+    for k, v in enumerate(values):
+        if v > values[best]:
+            best = k
+    return best
+
+
+def curve_from_hist(hist: torch.Tensor, thresholds: Sequence[float], beta: float = 0.5) -> Dict[str, torch.Tensor]:
+    """Everything BinarySegmentationCurve.compute() returns, from a histogram [..., 2, T + 1] on the host."""
+    counts = curve_counts(hist.cpu())
+    out = {"thresholds": torch.tensor(list(thresholds), dtype=torch.float64)}
+    out.update(counts)
+    out.update(curve_values(counts["tp"], counts["fp"], counts["fn"], counts["tn"], beta))
+    lead = counts["tp"].shape[:-1]
+    T = counts["tp"].shape[-1]
+    rows = [binned_average_precision(a, b, c) for a, b, c in
+            zip(counts["tp"].reshape(-1, T).tolist(), counts["fp"].reshape(-1, T).tolist(),
+                counts["fn"].reshape(-1, T).tolist())]
+    out["AveragePrecision"] = torch.tensor(rows, dtype=torch.float32).reshape(lead)
+    return out
+
+
+class BinarySegmentationCurve(nn.Module):
+    """The confusion counts of `thresholds` from ONE pass over the batch, and what follows from them: the
+    precision-recall curve, the binned average precision the reference's MetricCollection carries commented out
+    (`BinnedAveragePrecision(num_classes=1, thresholds=torch.linspace(0.5, 0.95, 20))`, utils/scripts_utils.py:90), and
+    the threshold that maximises a metric.  Semantics are BinarySegmentationMetrics' own: column k of every result equals
+    `BinarySegmentationMetrics(tau=thresholds[k], beta)` on the same updates, bit for bit (each threshold rounded to
+    pred's dtype, `>=`, NaN negative, targets truncated, bad preds / targets counted and raised by compute()).
+
+    update(pred, target) is one sn_binary_curve call (two launches, no synchronisation: it sits inside a captured
+    training step, CapturedTrainingStep(metrics=curve)); with per_tile=True the leading dimension of `pred` is the tile
+    count and every tile keeps a histogram of its own, in a state sized at the first update.  compute() synchronises
+    once (all-reduced over `process_group` first when it has more than one rank and sync_on_compute is set) and returns
+    {"thresholds" fp64 [T]; "tp", "fp", "fn", "tn" int64 [T]; "JaccardIndex", "Precision", "Recall", "F1Score",
+    "FBetaScore" fp32 [T]; "AveragePrecision" fp32 scalar}, with a leading [tiles] dimension on everything but the
+    thresholds when per_tile is set.  The average precision is our reading of torchmetrics 0.9's binned rule
+    (binned_average_precision); torchmetrics was not available to check against, so that reading is unpinned.
+    The state moves with .to(device) and adds no state-dict keys.  There is no CPU path."""
+
+    def __init__(self, thresholds=None, beta: float = 0.5, per_tile: bool = False, sync_on_compute: bool = True,
+                 process_group=None):
+        super().__init__()
+        if thresholds is None:
+            thresholds = torch.linspace(0.5, 0.95, 20)
+        self.thresholds = _check_thresholds(thresholds)
+        if not float(beta) > 0.0:
+            raise ValueError(f"beta must be positive (got {beta})")
+        self.beta, self.per_tile = float(beta), bool(per_tile)
+        self.sync_on_compute, self.process_group = bool(sync_on_compute), process_group
+        self._thr_c = None   # the ctypes table of the thresholds, built at the first update (never copied or pickled)
+        self._record = _hip.curve_record(len(self.thresholds))
+        # per tile: no rows until the first update has shown how many tiles a batch holds
+        self.register_buffer("state", torch.zeros((0 if self.per_tile else 1, self._record), dtype=torch.int64),
+                             persistent=False)
+        self.register_buffer("_ws", torch.zeros(0, dtype=torch.int64), persistent=False)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_thr_c"] = None
+        return state
+
+    @torch.no_grad()
+    def update(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        if pred.numel() != target.numel():
+            raise ValueError(f"pred ({pred.numel()} elements) and target ({target.numel()} elements) must have the same "
+                             "number of elements")
+        if pred.is_cuda and self.state.device != pred.device:
+            raise HipLibraryError(f"the curve state lives on {self.state.device}: move the module with "
+                                  f".to({pred.device}) first")
+        segments = 1
+        if self.per_tile:
+            if pred.dim() < 2:
+                raise ValueError("per_tile=True takes pred [tiles, ...]")
+            segments = int(pred.shape[0])
+            if self.state.shape[0] == 0:
+                self.state = torch.zeros((segments, self._record), dtype=torch.int64, device=self.state.device)
+            elif self.state.shape[0] != segments:
+                raise ValueError(f"the state holds {self.state.shape[0]} tiles; this batch has {segments} "
+                                 "(reset() keeps the tile count; build a new curve for another)")
+        T = len(self.thresholds)
+        if self._thr_c is None:
+            self._thr_c = (ctypes.c_double * T)(*self.thresholds)
+        need = _hip.curve_ws_bytes(pred.numel() // max(segments, 1), segments, T) if pred.numel() else 0
+        if self._ws.numel() * 8 < need:
+            self._ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=self.state.device)
+        _hip.binary_curve(pred.reshape(-1), target.reshape(-1), self._thr_c, self._ws, self.state, segments=segments)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        self.update(pred, target)
+
+    def _synced_state(self) -> torch.Tensor:
+        state = self.state.clone()
+        if self.sync_on_compute:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.process_group) > 1:
+                dist.all_reduce(state, op=dist.ReduceOp.SUM, group=self.process_group)
+        return state
+
+    def histogram(self) -> torch.Tensor:
+        """The accumulated histogram of THIS process, int64 [2, T + 1] ([tiles, 2, T + 1] per tile), on the host;
+        synchronises."""
+        T = len(self.thresholds)
+        h = self.state.cpu()[:, :2 * (T + 1)].reshape(-1, 2, T + 1)
+        return h if self.per_tile else h[0]
+
+    def compute(self) -> Dict[str, torch.Tensor]:
+        T = len(self.thresholds)
+        state = self._synced_state().cpu()
+        if int(state[:, 2 * (T + 1)].sum()):
+            raise ValueError(PRED_RANGE_ERROR)
+        if int(state[:, 2 * (T + 1) + 1].sum()):
+            raise ValueError(TARGET_RANGE_ERROR)
+        hist = state[:, :2 * (T + 1)].reshape(-1, 2, T + 1)
+        if int(hist.sum()) == 0:
+            warnings.warn("BinarySegmentationCurve.compute() was called before any update(); returning zeros",
+                          UserWarning)
+        out = curve_from_hist(hist if self.per_tile else hist[0], self.thresholds, self.beta)
+        dev = self.state.device
+        return {k: v.to(dev) for k, v in out.items()}
+
+    def average_precision(self) -> torch.Tensor:
+        return self.compute()["AveragePrecision"]
+
+    def best_threshold(self, metric: str = "F1Score"):
+        """(tau, value) of the threshold where `metric` is largest, ties to the lowest threshold; per tile: two tensors
+        [tiles] (fp64 thresholds, fp32 values).  Synchronises (compute())."""
+        if metric not in METRIC_NAMES:
+            raise KeyError(metric)
+        vals = self.compute()[metric].cpu()
+        if not self.per_tile:
+            k = best_index(vals.tolist())
+            return self.thresholds[k], float(vals[k])
+        ks = [best_index(row) for row in vals.tolist()]
+        return (torch.tensor([self.thresholds[k] for k in ks], dtype=torch.float64),
+                torch.stack([vals[i, k] for i, k in enumerate(ks)]) if ks else vals.new_zeros(0))
+
+    def at(self, tau: float) -> Dict[str, torch.Tensor]:
+        """{name: value} of the counts and the five values at a threshold of the list (KeyError otherwise)."""
+        if float(tau) not in self.thresholds:
+            raise KeyError(tau)
+        k = self.thresholds.index(float(tau))
+        res = self.compute()
+        return {n: res[n][..., k] for n in CURVE_COUNT_NAMES + METRIC_NAMES}
+
+    @torch.no_grad()
+    def reset(self) -> None:
+        self.state.zero_()
+
+    def extra_repr(self) -> str:
+        return (f"thresholds={len(self.thresholds)} in [{self.thresholds[0]:.4g}, {self.thresholds[-1]:.4g}], "
+                f"beta={self.beta}, per_tile={self.per_tile}")
