@@ -190,6 +190,25 @@ int sn_conv_bank(const void* x, int x_dtype, const float* bank, const float* lam
                  int B, int Z, int X, int Y, int G, int kz, int kx, int ky,
                  void* act, void* out, int out_dtype, sn_stream_t stream);
 
+/* What sn_conv_bank would launch for these arguments under the options in force now: host arithmetic only, no launch, no
+ * device memory; works without a device (the tile ladder then assumes 256 compute units).  It runs the planners the launch
+ * itself runs, so the two cannot disagree; pointers are taken to be aligned the way a fresh allocation is (16 bytes).  For
+ * G > 16 it describes the launch of the first group of 16 kernels.  plan8 (8 x int32, host memory):
+ *   [0] kernel: 0 the fp32 MFMA kernel, 1 the four-copy int8 kernel, 2 the stride-4 int8 kernel, 3 the folded int8 kernel
+ *       (the host's half of that choice: the launch is the folded kernel's, which checks the bank's x/y symmetry on the
+ *       device and runs the stride-4 body in place, on the same tiles, for a bank that is not symmetric).  The guards that
+ *       hand an int8 launch to the fp32 kernel on the device (conv_i8_tolerance_ppb) are not part of the plan
+ *   [1] TZ, [2] TX: z and x extent of a workgroup tile (its y extent is always 64)
+ *   [3] number of workgroup tiles: B * ceil(Z / TZ) * ceil(X / TX) * ceil(Y / 64)
+ *   [4] flags: bit 0 the fp32 kernel's double-buffered form, bit 1 the halo is staged by LDS-DMA
+ *   [5] stride of a halo row in LDS, bytes
+ *   [6] compute units the tile ladder counted (the first rung with [3] >= 4 * [6] is taken)
+ *   [7] 0 (reserved)
+ * Returns SN_OK, SN_ERR_INVALID_ARG (null plan8, an extent <= 0, unknown x_dtype) or SN_ERR_UNSUPPORTED where sn_conv_bank
+ * returns it (ky > 25, kernel does not fit LDS).  No reference counterpart (F.conv3d has no tile plan to ask about): this is
+ * what lets a test reach, and name, every tile the hand-written kernels can pick. */
+int sn_conv_bank_plan(int x_dtype, int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8);
+
 /* The same contraction for a bank whose per-bank work was done once, ahead of the launch (round 3).
  * SceneNet.forward rebuilds its kernels from the parameters on every call (SCENE_Net.py:322-327); everything the int8
  * contraction derives from the bank alone -- the x/y symmetry verdict, the 24-bit fixed-point weights, the worst-case

@@ -10,7 +10,7 @@ import ctypes
 import functools
 import os
 from ctypes import c_char_p, c_int, c_void_p
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -39,6 +39,7 @@ SYMBOLS = {
     "sn_geneo_bank": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "sn_effective_lambdas": (c_int, [_P, _P, _I, _I, _P, _P]),
     "sn_conv_bank": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "sn_conv_bank_plan": (c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sn_geneo_bank_prep": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "sn_conv_bank_prep": (c_int, [_P, _I, _I, _I, _I, _P, _P]),
     "sn_conv_bank_prepared": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
@@ -457,6 +458,41 @@ def conv_bank(x: torch.Tensor, bank: torch.Tensor, lambdas: Optional[torch.Tenso
                              _ptr(act, None, "act"), _ptr(out, None, "out"), _DT_OUT[out_dtype], _stream())
     _check(rc, "sn_conv_bank")
     return act, out
+
+
+class ConvPlan(NamedTuple):
+    """sn_conv_bank_plan's eight words (include/scenenet_hip.h)."""
+    kernel: str          # "fp32" | "four_copy" | "stride4" | "folded"
+    tz: int
+    tx: int
+    ntiles: int
+    double_buffered: bool
+    staged: bool         # halo staged by LDS-DMA
+    row_stride: int      # bytes of a halo row in LDS
+    cus: int             # compute units the tile ladder counted
+
+    @property
+    def rung(self) -> Tuple[int, int]:
+        return (self.tz, self.tx)
+
+
+CONV_PLAN_KERNELS = ("fp32", "four_copy", "stride4", "folded")
+
+
+def conv_bank_plan(x, bank_shape: Sequence[int]) -> ConvPlan:
+    """What conv_bank(x, bank) would launch under the options in force (sn_conv_bank_plan: host only, no launch, no device
+    needed).  x: a [B,1,Z,X,Y] tensor on any device, or (dtype, shape); bank_shape: (G, kz, kx, ky)."""
+    dtype, shape = (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else (x[0], tuple(x[1]))
+    if len(shape) != 5 or shape[1] != 1:
+        raise HipLibraryError(f"x must be [B,1,Z,X,Y] (got {shape})")
+    if dtype not in _DT or dtype == torch.bfloat16:
+        raise HipLibraryError(f"x dtype {dtype} unsupported (f32, f64, u8, bool)")
+    B, _, Z, X, Y = (int(v) for v in shape)
+    G, kz, kx, ky = (int(v) for v in bank_shape)
+    p = (ctypes.c_int32 * 8)()
+    _check(load().sn_conv_bank_plan(_DT[dtype], B, Z, X, Y, G, kz, kx, ky, ctypes.cast(p, c_void_p)), "sn_conv_bank_plan")
+    return ConvPlan(CONV_PLAN_KERNELS[p[0]], int(p[1]), int(p[2]), int(p[3]), bool(p[4] & 1), bool(p[4] & 2), int(p[5]),
+                    int(p[6]))
 
 
 def conv_fused_supported(x: torch.Tensor, kernel_size: Sequence[int]) -> bool:

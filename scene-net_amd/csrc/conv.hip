@@ -72,6 +72,8 @@ int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B
 int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int B, int Z, int X, int Y, int G, int Gtot,
                  int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype,
                  hipStream_t stream);  // conv_i8s.hip
+int conv_occ_i8_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8);    // conv_i8.hip
+int conv_occ_i8s_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8);   // conv_i8s.hip
 int conv_bank_group(const void* x, int x_dtype, const float* bank, const float* lambdas, int B, int Z, int X, int Y,
                     int G, int Gtot, int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype,
                     sn_stream_t stream);
@@ -145,4 +147,35 @@ int sn::conv_bank_group(const void* x, int x_dtype, const float* bank, const flo
         default: return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank: x_dtype %d", x_dtype);
     }
 #undef SN_DISPATCH
+}
+
+// What sn_conv_bank would launch, from the same planners the launch calls (the dispatch below mirrors conv_bank_group's,
+// step for step); pointers are taken to be aligned as torch allocates them.  Host only.
+extern "C" int sn_conv_bank_plan(int x_dtype, int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8) {
+    if (!plan8) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_plan: null plan8");
+    if (B <= 0 || Z <= 0 || X <= 0 || Y <= 0 || G <= 0 || kz <= 0 || kx <= 0 || ky <= 0)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_plan: non-positive extent");
+    if (ky - 1 > YP - TY) return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_bank_plan: ky=%d > %d", ky, YP - TY + 1);
+    if ((size_t)B * Z * X * Y > (size_t)1 << 40) return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_bank_plan: grid too large");
+    const int Gtot = G, head = G > 16 ? 0 : 2;
+    if (G > 16) G = 16;   // the first group's launch
+    switch (x_dtype) {
+        case SN_F32: case SN_F64: case SN_U8: break;
+        case SN_OCC8:
+            if (!sn::option(sn::kOptConvNoI8)) {
+                if (!sn::option(sn::kOptConvI8Legacy) && sn::conv_occ_i8s_plan(B, Z, X, Y, G, kz, kx, ky, plan8) == 0)
+                    return SN_OK;
+                if (sn::conv_occ_i8_plan(B, Z, X, Y, G, kz, kx, ky, plan8) == 0) return SN_OK;
+            }
+            break;
+        default: return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_plan: x_dtype %d", x_dtype);
+    }
+    ConvShape s;
+    bool dbl = false;
+    if (!plan_fp32(s, B, Z, X, Y, G, Gtot, 0, head, kz, kx, ky, num_cus(), sn::option(sn::kOptConvDoubleBuffer) != 0, dbl))
+        return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_bank_plan: kernel %dx%dx%d does not fit the 160 KiB LDS tile", kz, kx,
+                        ky);
+    plan8[0] = 0; plan8[1] = s.TZ; plan8[2] = s.TX; plan8[3] = s.ntiles;
+    plan8[4] = dbl ? 1 : 0; plan8[5] = YP * (int)sizeof(float); plan8[6] = num_cus(); plan8[7] = 0;
+    return SN_OK;
 }

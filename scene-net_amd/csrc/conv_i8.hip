@@ -677,34 +677,21 @@ int num_cus() {
     return cached;
 }
 
-}  // namespace
-
-namespace sn {
-
-int conv_bank_group(const void* x, int x_dtype, const float* bank, const float* lambdas, int B, int Z, int X, int Y,
-                    int G, int Gtot, int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype,
-                    sn_stream_t stream);   // conv.hip
-
-// returns SN_OK, an error, or 1 when this shape is not served by the int8 kernel (caller falls back to fp32)
-int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B, int Z, int X, int Y, int G, int Gtot,
-                int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype, hipStream_t stream) {
-    if (Y % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 3) != 0 || G > 16) return 1;
-    Shape s;
-    s.B = B; s.Z = Z; s.X = X; s.Y = Y; s.G = G; s.kz = kz; s.kx = kx; s.ky = ky;
-    s.Gtot = Gtot; s.g0 = g0; s.head = head;
-    s.gate = sn::current_gate();
+// Tile and variant of the four-copy kernel for the grid, bank and kernel extents already in `s` (B, Z, X, Y, G, kz, kx, ky):
+// fills the derived fields (C, R, KS, PYA, delta, nyt, TZ, TX, nzt, nxt, ntiles, XPAD, CB) and reports the halo row stride
+// and whether the LDS-DMA staged template runs.  false = shape not served here.  The launch (conv_occ_i8) and the plan
+// query (conv_occ_i8_plan, for sn_conv_bank_plan) both call this: there is no second copy of the ladder.
+bool plan_four_copy(Shape& s, int cus, bool nostage, int& ypb_out, bool& stage_out) {
+    const int B = s.B, Z = s.Z, X = s.X, kz = s.kz, kx = s.kx, ky = s.ky;
+    if (s.Y % 4 != 0 || s.G > 16) return false;
     s.C = (ky + 3) / 4;
-    if (s.C > kMaxC) return 1;
+    if (s.C > kMaxC) return false;
     s.R = kz * kx;
     s.KS = (((s.R * s.C + 15) / 16) + 1) & ~1;
     const int py = (ky - 1) / 2;
     s.PYA = (py + 3) & ~3;
     s.delta = s.PYA - py;
-    s.nyt = (Y + TY - 1) / TY;
-    s.dbg = sn::debug_env_int("SN_CONV_I8_DBG");   // (0 in the product: common.h)
-    s.skip_empty = sn::option(sn::kOptConvSkipEmptyTiles);
-    const bool nostage = sn::option(sn::kOptConvI8NoStage) != 0;
-    const int cus = num_cus();
+    s.nyt = (s.Y + TY - 1) / TY;
     const int need = s.delta + 15 + 48 + 4 * s.C + 3;  // bytes of a halo row the reads can touch
     // variants in order of preference: (row stride, LDS-DMA staging)
     const int variants[][2] = {{80, 1}, {96, 0}};
@@ -740,28 +727,57 @@ int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B
         }
         // staging only pays with the big tile (several rounds per wave between barriers); otherwise try the next
         if (!found || (stage && (s.TZ != 8 || s.TX != 8))) continue;
-        const int grid = cus < s.ntiles ? cus : s.ntiles;
-        const size_t lds = lds_bytes(s, ypb, stage);
-        s.perm = 1;
-        for (int cand_p : {97, 101, 103, 107, 109, 113, 127, 131})
-            if (s.ntiles % cand_p != 0) { s.perm = cand_p; break; }  // primes: coprime unless they divide ntiles
-        // dynamic tile scheduling when tile costs are data dependent: a ticket counter, zeroed on the launch stream.
-        // Counters come from a per-device ring allocated once (the only state this opt-in mode keeps): 1024 launches
-        // may be in flight before a slot is reused.
-        int* ticket = nullptr;
-        if (s.skip_empty && s.ntiles > grid) {
-            ticket = sn::device_flag_slot(stream);
-            if (ticket && hipMemsetAsync(ticket, 0, sizeof(int), stream) != hipSuccess) {
-                (void)hipGetLastError();
-                ticket = nullptr;  // static order still gives the right answer
-            }
+        ypb_out = ypb;
+        stage_out = stage;
+        return true;
+    }
+    return false;
+}
+
+}  // namespace
+
+namespace sn {
+
+int conv_bank_group(const void* x, int x_dtype, const float* bank, const float* lambdas, int B, int Z, int X, int Y,
+                    int G, int Gtot, int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype,
+                    sn_stream_t stream);   // conv.hip
+
+// returns SN_OK, an error, or 1 when this shape is not served by the int8 kernel (caller falls back to fp32)
+int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B, int Z, int X, int Y, int G, int Gtot,
+                int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype, hipStream_t stream) {
+    if ((reinterpret_cast<uintptr_t>(x) & 3) != 0) return 1;
+    Shape s;
+    s.B = B; s.Z = Z; s.X = X; s.Y = Y; s.G = G; s.kz = kz; s.kx = kx; s.ky = ky;
+    s.Gtot = Gtot; s.g0 = g0; s.head = head;
+    s.gate = sn::current_gate();
+    s.dbg = sn::debug_env_int("SN_CONV_I8_DBG");   // (0 in the product: common.h)
+    s.skip_empty = sn::option(sn::kOptConvSkipEmptyTiles);
+    const int cus = num_cus();
+    int ypb = 0;
+    bool stage = false;
+    if (!plan_four_copy(s, cus, sn::option(sn::kOptConvI8NoStage) != 0, ypb, stage)) return 1;
+    const int grid = cus < s.ntiles ? cus : s.ntiles;
+    const size_t lds = lds_bytes(s, ypb, stage);
+    s.perm = 1;
+    for (int cand_p : {97, 101, 103, 107, 109, 113, 127, 131})
+        if (s.ntiles % cand_p != 0) { s.perm = cand_p; break; }  // primes: coprime unless they divide ntiles
+    // dynamic tile scheduling when tile costs are data dependent: a ticket counter, zeroed on the launch stream.
+    // Counters come from a per-device ring allocated once (the only state this opt-in mode keeps): 1024 launches
+    // may be in flight before a slot is reused.
+    int* ticket = nullptr;
+    if (s.skip_empty && s.ntiles > grid) {
+        ticket = sn::device_flag_slot(stream);
+        if (ticket && hipMemsetAsync(ticket, 0, sizeof(int), stream) != hipSuccess) {
+            (void)hipGetLastError();
+            ticket = nullptr;  // static order still gives the right answer
         }
-        s.tol = sn::conv_i8_tolerance();
-        s.route = nullptr;
-        if (s.tol > 0.0f) {
-            s.route = sn::device_flag_slot(stream);
-            if (!s.route) s.tol = 0.0f;   // no flag memory: run unguarded rather than fail
-        }
+    }
+    s.tol = sn::conv_i8_tolerance();
+    s.route = nullptr;
+    if (s.tol > 0.0f) {
+        s.route = sn::device_flag_slot(stream);
+        if (!s.route) s.tol = 0.0f;   // no flag memory: run unguarded rather than fail
+    }
 #define SN_LAUNCH_I8(OT, YPBV, STG)                                                                              \
     do {                                                                                                         \
         auto kern = conv_occ_i8_kernel<OT, YPBV, STG>;                                                           \
@@ -770,21 +786,33 @@ int conv_occ_i8(const uint8_t* x, const float* bank, const float* lambdas, int B
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, x, bank, lambdas, s, ticket,           \
                            (OT*)act, (OT*)out);                                                                  \
     } while (0)
-        if (out_dtype == SN_F32) {
-            if (stage) SN_LAUNCH_I8(float, 80, true); else SN_LAUNCH_I8(float, 96, false);
-        } else {
-            if (stage) SN_LAUNCH_I8(double, 80, true); else SN_LAUNCH_I8(double, 96, false);
-        }
-#undef SN_LAUNCH_I8
-        if (int rc = check_launch("sn_conv_bank(i8)")) return rc;
-        if (s.route) {   // the same launch on the fp32 matrix pipe, enqueued behind: runs only if the guard sent it there
-            sn::GateScope guard(s.route, 1);
-            return sn::conv_bank_group(x, SN_U8, bank, lambdas, B, Z, X, Y, G, Gtot, g0, head, kz, kx, ky, act, out,
-                                       out_dtype, reinterpret_cast<sn_stream_t>(stream));
-        }
-        return SN_OK;
+    if (out_dtype == SN_F32) {
+        if (stage) SN_LAUNCH_I8(float, 80, true); else SN_LAUNCH_I8(float, 96, false);
+    } else {
+        if (stage) SN_LAUNCH_I8(double, 80, true); else SN_LAUNCH_I8(double, 96, false);
     }
-    return 1;
+#undef SN_LAUNCH_I8
+    if (int rc = check_launch("sn_conv_bank(i8)")) return rc;
+    if (s.route) {   // the same launch on the fp32 matrix pipe, enqueued behind: runs only if the guard sent it there
+        sn::GateScope guard(s.route, 1);
+        return sn::conv_bank_group(x, SN_U8, bank, lambdas, B, Z, X, Y, G, Gtot, g0, head, kz, kx, ky, act, out,
+                                   out_dtype, reinterpret_cast<sn_stream_t>(stream));
+    }
+    return SN_OK;
+}
+
+// sn_conv_bank_plan's view of the four-copy kernel: what conv_occ_i8 would launch for a suitably aligned x.  0 = plan8 filled,
+// 1 = shape not served here.
+int conv_occ_i8_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8) {
+    Shape s;
+    s.B = B; s.Z = Z; s.X = X; s.Y = Y; s.G = G; s.kz = kz; s.kx = kx; s.ky = ky;
+    const int cus = num_cus();
+    int ypb = 0;
+    bool stage = false;
+    if (!plan_four_copy(s, cus, sn::option(sn::kOptConvI8NoStage) != 0, ypb, stage)) return 1;
+    plan8[0] = 1; plan8[1] = s.TZ; plan8[2] = s.TX; plan8[3] = s.ntiles;
+    plan8[4] = stage ? 2 : 0; plan8[5] = ypb; plan8[6] = cus; plan8[7] = 0;
+    return 0;
 }
 
 }  // namespace sn

@@ -160,6 +160,21 @@ bool plan_stride4(Shape& s, int B, int Z, int X, int Y, int kz, int kx, int cus)
     return found;
 }
 
+// What the arguments alone decide (pointer alignment aside): a shape of the stride-4 kernel?  The launch and the plan query
+// (conv_occ_i8s_plan) both ask here.
+bool stride4_shape(int Y, int G, int kz, int kx, int ky) {
+    if (ky != 9 || kz * kx != 81 || Y % 16 != 0 || G > 16) return false;
+    return !sn::option(sn::kOptConvSkipEmptyTiles);   // data-dependent tile skipping lives in conv_i8.hip
+}
+
+// The host's part of "the folded kernel takes this launch" for a planned Shape (the bank's symmetry is the device's part):
+// ldsf = the LDS the folded launch asks for (it may run the stride-4 body).
+bool fold_fits(const Shape& s, size_t& ldsf) {
+    ldsf = lds_bytes_fold(s) > lds_bytes(s) ? lds_bytes_fold(s) : lds_bytes(s);
+    return s.kz == 9 && s.kx == 9 && sn::option(sn::kOptConvI8Fold) && ldsf <= (size_t)kMaxLds &&
+           (s.XP == 17 || s.XP == 13 || s.XP == 11);
+}
+
 #include "conv_i8z.inc"
 
 }  // namespace
@@ -169,14 +184,14 @@ namespace sn {
 int conv_bank_group(const void* x, int x_dtype, const float* bank, const float* lambdas, int B, int Z, int X, int Y,
                     int G, int Gtot, int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype,
                     sn_stream_t stream);   // conv.hip
+int conv_occ_i8s_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8);
 
 // returns SN_OK, an error, or 1 when this shape is not served here (caller tries conv_occ_i8, then fp32)
 int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int B, int Z, int X, int Y, int G, int Gtot,
                  int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype, hipStream_t stream) {
-    if (ky != 9 || kz * kx != 81 || Y % 16 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || G > 16) return 1;
+    if (!stride4_shape(Y, G, kz, kx, ky) || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return 1;
     if (act && (reinterpret_cast<uintptr_t>(act) & 15)) return 1;
     if (out && (reinterpret_cast<uintptr_t>(out) & 15)) return 1;
-    if (sn::option(sn::kOptConvSkipEmptyTiles)) return 1;   // data-dependent tile skipping lives in conv_i8.hip
     Shape s;
     memset(&s, 0, sizeof(s));
     s.B = B; s.Z = Z; s.X = X; s.Y = Y; s.G = G; s.kz = kz; s.kx = kx;
@@ -197,15 +212,14 @@ int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int 
     // 1. the folded kernel (banks symmetric in x and y: every GENEO bank) -- it checks the symmetry on the device, runs the
     //    stride-4 body itself for a bank that is not, and leaves *flag = 0 (served) or 1 (bound exceeded: fp32 kernel)
     int32_t* flag = sn::device_flag_slot(stream);
-    const bool fold = kz == 9 && kx == 9 && flag && sn::option(sn::kOptConvI8Fold) &&
-                      s.dbg == 0;   // (the debug switches belong to the stride-4 kernel)
+    size_t ldsf = 0;
+    const bool fold = flag && s.dbg == 0 &&   // (the debug switches belong to the stride-4 kernel)
+                      fold_fits(s, ldsf);
     bool folded = false;
     if (fold) {
         Shape sf = s;
         plan_fold(sf.XP, sf.fplan);
         sf.route = flag;
-        const size_t ldsf = lds_bytes_fold(sf) > lds_bytes(s) ? lds_bytes_fold(sf) : lds_bytes(s);   // (it may run the stride-4 body)
-        if (ldsf <= (size_t)kMaxLds && (sf.XP == 17 || sf.XP == 13 || sf.XP == 11)) {
 #define SN_LAUNCH_I8F(OT, XPV)                                                                                   \
     do {                                                                                                         \
         auto kern = conv_occ_i8f_kernel<OT, XPV>;                                                                \
@@ -219,14 +233,13 @@ int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int 
         if (out_dtype == SN_F32) SN_LAUNCH_I8F(float, XPV);                                                      \
         else SN_LAUNCH_I8F(double, XPV);                                                                         \
     } while (0)
-            if (sf.XP == 17) SN_LAUNCH_I8F_XP(17);        // TX = 8
-            else if (sf.XP == 13) SN_LAUNCH_I8F_XP(13);   // TX = 4
-            else SN_LAUNCH_I8F_XP(11);                    // TX = 2
+        if (sf.XP == 17) SN_LAUNCH_I8F_XP(17);        // TX = 8
+        else if (sf.XP == 13) SN_LAUNCH_I8F_XP(13);   // TX = 4
+        else SN_LAUNCH_I8F_XP(11);                    // TX = 2
 #undef SN_LAUNCH_I8F_XP
 #undef SN_LAUNCH_I8F
-            if (int rc = check_launch("sn_conv_bank(i8f)")) return rc;
-            folded = true;
-        }
+        if (int rc = check_launch("sn_conv_bank(i8f)")) return rc;
+        folded = true;
     }
     // 2. the stride-4 kernel as its own launch, when the folded kernel was not tried (it runs the stride-4 body itself for
     //    a bank it declines)
@@ -381,6 +394,25 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
 }
 
 }  // namespace sn
+
+// sn_conv_bank_plan's view of the stride-4 / folded kernels: what conv_occ_i8s would launch for suitably aligned pointers.
+// 0 = plan8 filled, 1 = shape not served here.
+int sn::conv_occ_i8s_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8) {
+    if (!stride4_shape(Y, G, kz, kx, ky)) return 1;
+    Shape s;
+    memset(&s, 0, sizeof(s));
+    s.B = B; s.Z = Z; s.X = X; s.Y = Y; s.G = G; s.kz = kz; s.kx = kx;
+    s.nyt = (Y + TY - 1) / TY;
+    const int cus = num_cus();
+    if (!plan_stride4(s, B, Z, X, Y, kz, kx, cus)) return 1;
+    size_t ldsf = 0;
+    plan8[0] = fold_fits(s, ldsf) ? 3 : 2;
+    plan8[1] = s.TZ; plan8[2] = s.TX; plan8[3] = s.ntiles;
+    plan8[4] = 2;           // both fill their halo ring by LDS-DMA
+    plan8[5] = 4 * DW;      // bytes of a halo row
+    plan8[6] = cus; plan8[7] = 0;
+    return 0;
+}
 
 extern "C" int sn_conv_bank_prep(const float* bank, int G, int kz, int kx, int ky, void* prep, sn_stream_t stream) {
     if (!bank || !prep) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_prep: null pointer");
