@@ -243,6 +243,12 @@ int sn_conv_prep_verdict_offset(void);
  * not silent: it latches the sticky device status (code 1 / 3, above), and the z-walk overwrites its workgroup's outputs
  * with NaN.  Synchronises the device. */
 int sn_conv_i8_spin_timeouts(unsigned long long* count);
+/* Diagnostics: how many workgroups of the one-pass voxelisation kernel (sn_voxel_occupancy_fused[_bank] at grids whose bitmap
+ * fits one workgroup) ever gave up the bounded wait of the box exchange and took their tile's box from the points themselves
+ * -- the same bits, one more pass over the tile.  0 in normal use; every workgroup with option voxel_onepass_spin = 0.
+ * Counted by the kernel itself (no launch of its own), in a word of the CURRENT device: the count is per device and per
+ * process, cumulative from the library's load -- there is no reset, compare two readings.  Synchronises the device. */
+int sn_voxel_onepass_giveups(unsigned long long* count);
 
 /* Measurement hook: the NEXT z-walk launch of the calling thread (sn_conv_bank_prepared[_served] on a 9^3 bank) is made with
  * hipExtLaunchKernel(..., start_event, stop_event): the two hipEvent_t (created by the caller; either may be null) receive

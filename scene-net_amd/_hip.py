@@ -46,6 +46,7 @@ SYMBOLS = {
     "sn_conv_bank_prepared_served": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "sn_conv_prep_verdict_offset": (c_int, []),
     "sn_conv_i8_spin_timeouts": (c_int, [_P]),
+    "sn_voxel_onepass_giveups": (c_int, [_P]),
     "sn_launch_timing_events": (c_int, [_P, _P]),
     "sn_conv_fused": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sn_conv_fused_supported": (c_int, [_I, _I, _I, _I, _I, _I, _I]),
@@ -199,6 +200,14 @@ def conv_i8_spin_timeouts() -> int:
     """Waves of the int8 kernels that ever gave up a bounded LDS hand-over spin (must be 0); synchronises."""
     buf = (ctypes.c_ulonglong * 1)()
     _check(load().sn_conv_i8_spin_timeouts(ctypes.cast(buf, ctypes.c_void_p)), "sn_conv_i8_spin_timeouts")
+    return int(buf[0])
+
+
+def voxel_onepass_giveups() -> int:
+    """Workgroups of the one-pass voxelisation kernel that ever gave up the box exchange's bounded wait and took their tile's
+    box from the points alone (same bits; 0 in normal use, every workgroup with voxel_onepass_spin = 0); synchronises."""
+    buf = (ctypes.c_ulonglong * 1)()
+    _check(load().sn_voxel_onepass_giveups(ctypes.cast(buf, ctypes.c_void_p)), "sn_voxel_onepass_giveups")
     return int(buf[0])
 
 

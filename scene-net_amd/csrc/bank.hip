@@ -25,8 +25,8 @@ __global__ __launch_bounds__(kThreads) void geneo_bank_kernel(const float* __res
                                                               const int32_t* __restrict__ order, int last,
                                                               float* __restrict__ lambdas_out,
                                                               uint8_t* __restrict__ prep) {
-    extern __shared__ float lds[];
-    geneo_bank_body<kPrep>(lds, blockIdx.x, threadIdx.x, params, kinds, kz, kx, ky, bank, status, G, lambdas, order, last,
+    extern __shared__ __align__(16) float lds[];
+    geneo_bank_body<kPrep>(lds, blockIdx.x, threadIdx.x, kThreads, params, kinds, kz, kx, ky, bank, status, G, lambdas, order, last,
                            lambdas_out, prep);
 }
 
@@ -85,7 +85,7 @@ extern "C" int sn_geneo_bank_prep(const float* params, const int32_t* kinds, int
         return sn::fail(SN_ERR_UNSUPPORTED, "sn_geneo_bank_prep: the prepared contraction serves 9 x 9 x 9 kernels (got %d,%d,%d)", kz,
                         kx, ky);
     if (reinterpret_cast<uintptr_t>(prep) & 15) return sn::fail(SN_ERR_INVALID_ARG, "sn_geneo_bank_prep: prep must be 16-byte aligned");
-    const size_t lds = (size_t)(729 + kz + 1 + 8) * sizeof(float);
+    const size_t lds = (size_t)kBankPrepLdsFloats * sizeof(float);
     const int ngeneo = 16 * ((G + 15) / 16);
     hipLaunchKernelGGL(geneo_bank_kernel<true>, dim3(ngeneo + (lambdas ? 1 : 0)), dim3(kThreads), lds, sn::as_stream(stream),
                        params, kinds, kz, kx, ky, bank, status, G, lambdas, order, last, lambdas_out,

@@ -1,6 +1,6 @@
 // K2's device code, shared by bank.hip (its own kernels) and voxel.hip (the rider form): included inside the includer's
 // anonymous namespace, after conv_prep.h.
-constexpr int kBankThreads = 256;
+constexpr int kBankThreads = SN_BANK_THREADS;   // the stand-alone kernels' workgroup (conv_prep.h)
 constexpr float kEps = 1e-8f;        // default `epsilon` of the v2 gaussians
 constexpr float kPi = 3.14159274f;   // torch.pi rounded to fp32 by the fp32 multiply
 
@@ -39,11 +39,15 @@ __device__ void effective_lambdas_thread(float* __restrict__ lambdas, const int3
 // kPrep (sn_geneo_bank_prep, 9 x 9 x 9 kernels): grid 16 ceil(G / 16) (+ 1); every workgroup g < 16 ceil(G / 16) also
 // prepares kernel g for the int8 contraction (conv_prep.h) from the weights it has just built, still in LDS --
 // workgroups G .. write the zero entries of the last group of 16.
-// (the body of geneo_bank_kernel: workgroup g, thread tid of kBankThreads, `lds` = 729 + kz + 1 + 8 floats of LDS (vol + kz
-// + 1 without the preparation) -- a function of its own so that K1's first launch can carry these workgroups as riders:
-// bbox_partial_bank_kernel, voxel.hip)
+// (the body of geneo_bank_kernel: workgroup g, thread tid of nthreads -- a multiple of 64, whatever the host workgroup has:
+// the loops stride by it, and a 9 x 9 x 9 kernel is one trip per phase for 1024 -- `lds` = kBankPrepLdsFloats floats of LDS,
+// 16-byte aligned (vol + kz + 1 without the preparation) -- a function of its own so that K1's first launch can carry
+// these workgroups as riders: bbox_partial_bank_kernel, occ_onepass_kernel, voxel.hip)
+constexpr int kBankPrepScr = 740;   // vals [729], seg_sum [9], then the preparation's scratch on a 16-byte boundary
+constexpr int kBankPrepLdsFloats = kBankPrepScr + kPrepScratchWords;
 template <bool kPrep>
-__device__ __forceinline__ void geneo_bank_body(float* lds, const int g, const int tid, const float* __restrict__ params,
+__device__ __forceinline__ void geneo_bank_body(float* lds, const int g, const int tid, const int nthreads,
+                                                const float* __restrict__ params,
                                                 const int32_t* __restrict__ kinds, int kz, int kx, int ky,
                                                 float* __restrict__ bank, int32_t* __restrict__ status, int G,
                                                 float* __restrict__ lambdas, const int32_t* __restrict__ order, int last,
@@ -53,13 +57,17 @@ __device__ __forceinline__ void geneo_bank_body(float* lds, const int g, const i
         if (tid == 0 && lambdas) effective_lambdas_thread(lambdas, order, G, last, lambdas_out);
         return;
     }
+    SN_BT(0);
     if constexpr (kPrep) {
         if (g >= G) {   // a pad entry of the last group of 16: all-zero kernel
-            for (int i = tid; i < 729; i += kBankThreads) lds[i] = 0.0f;
-            prep_one_kernel(lds, reinterpret_cast<int*>(lds + 732), false, g & 15, prep + (size_t)(g >> 4) * SN_CONV_PREP_BYTES,
-                            tid);
+            for (int i = tid; i < 729; i += nthreads) lds[i] = 0.0f;
+            SN_BT(1);   // (no phases 1..3 here: their clocks read the start of the preparation, never an earlier launch's)
+            SN_BT(2);
+            SN_BT(3);
+            prep_one_kernel(lds, lds + kBankPrepScr, false, g & 15, prep + (size_t)(g >> 4) * SN_CONV_PREP_BYTES, tid, nthreads);
             return;
         }
+        kz = kx = ky = 9;   // (checked by the host: the divisions below become multiply-shifts)
     }
     const int nfloor = kx * ky;
     const int vol = kz * nfloor;
@@ -90,7 +98,7 @@ __device__ __forceinline__ void geneo_bank_body(float* lds, const int g, const i
         if (is_neg) neg = p[SN_P_NEG_FACTOR];
     }
 
-    for (int idx = tid; idx < vol; idx += kBankThreads) {
+    for (int idx = tid; idx < vol; idx += nthreads) {
         float v;
         if (is_neg) {
             // output element idx of the row-major [kz,kx,ky] view takes flat-column row idx, whose
@@ -120,20 +128,22 @@ __device__ __forceinline__ void geneo_bank_body(float* lds, const int g, const i
         vals[idx] = v;
     }
     __syncthreads();
+    SN_BT(1);
 
     const int nseg = is_neg ? 1 : kz;
     const int seg_len = is_neg ? vol : nfloor;
     const int wave = tid >> 6, lane = tid & 63;
-    for (int s = wave; s < nseg; s += kBankThreads / 64) {
+    for (int s = wave; s < nseg; s += nthreads / 64) {   // one wave per segment
         float acc = 0.f;
         for (int i = lane; i < seg_len; i += 64) acc += vals[s * seg_len + i];
         acc = wave_sum(acc);
         if (lane == 0) seg_sum[s] = acc;
     }
     __syncthreads();
+    SN_BT(2);
 
     float* out = bank + (size_t)g * vol;
-    for (int idx = tid; idx < vol; idx += kBankThreads) {
+    for (int idx = tid; idx < vol; idx += nthreads) {
         float mean;
         if (kind == SN_GENEO_NEG)
             mean = (seg_sum[0] + neg) / (float)vol;  // sum_negfactor, neg_sphere.py:181-182
@@ -145,7 +155,8 @@ __device__ __forceinline__ void geneo_bank_body(float* lds, const int g, const i
         out[idx] = wv;
         if constexpr (kPrep) vals[idx] = wv;   // (each thread rewrites only what it read: the means are in seg_sum)
     }
-    if constexpr (kPrep)   // vol == 729 (checked by the host); seg_sum is dead after the loop's barrier inside
-        prep_one_kernel(vals, reinterpret_cast<int*>(seg_sum + kz), true, g & 15, prep + (size_t)(g >> 4) * SN_CONV_PREP_BYTES, tid);
+    SN_BT(3);
+    if constexpr (kPrep)   // vol == 729 (checked by the host)
+        prep_one_kernel(vals, lds + kBankPrepScr, true, g & 15, prep + (size_t)(g >> 4) * SN_CONV_PREP_BYTES, tid, nthreads);
 }
 

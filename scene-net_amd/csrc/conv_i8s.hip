@@ -421,7 +421,7 @@ extern "C" int sn_conv_bank_prep(const float* bank, int G, int kz, int kx, int k
     if (kz != 9 || kx != 9 || ky != 9) return SN_OK;   // other shapes: sn_conv_bank_prepared does not read the blob
     for (int g0 = 0; g0 < G; g0 += 16) {
         const int gc = (G - g0 < 16) ? G - g0 : 16;
-        hipLaunchKernelGGL(conv_prep_kernel, dim3(16), dim3(256), 0, sn::as_stream(stream), bank + (size_t)g0 * 729, gc,
+        hipLaunchKernelGGL(conv_prep_kernel, dim3(16), dim3(kPrepThreads), 0, sn::as_stream(stream), bank + (size_t)g0 * 729, gc,
                            static_cast<uint8_t*>(prep) + (size_t)(g0 / 16) * SN_CONV_PREP_BYTES);
     }
     return sn::check_launch("sn_conv_bank_prep");

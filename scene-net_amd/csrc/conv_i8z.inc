@@ -94,13 +94,14 @@ __device__ __forceinline__ int zjob_id(const ZShape& z, int wg, int k, int grid)
 // ------------------------------------------------------------------------------------------------ preparation kernel
 // One workgroup per kernel g (always 16 workgroups: g >= G writes zero entries); the work itself is prep_one_kernel
 // (conv_prep.h), which the GENEO bank builder also runs as its tail (sn_geneo_bank_prep).  ~3 us.
-__global__ __launch_bounds__(256) void conv_prep_kernel(const float* __restrict__ bank, int G, uint8_t* __restrict__ prep) {
-    __shared__ float w[736];
-    __shared__ int asym_s;
+constexpr int kPrepThreads = SN_BANK_THREADS;   // (conv_prep.h)
+__global__ __launch_bounds__(kPrepThreads) void conv_prep_kernel(const float* __restrict__ bank, int G,
+                                                                 uint8_t* __restrict__ prep) {
+    __shared__ __align__(16) float w[732 + kPrepScratchWords];
     const int g = blockIdx.x, tid = threadIdx.x;
     const bool valid = g < G;
-    for (int i = tid; i < 729; i += 256) w[i] = valid ? bank[(size_t)g * 729 + i] : 0.0f;
-    prep_one_kernel(w, &asym_s, valid, g, prep, tid);
+    for (int i = tid; i < 729; i += kPrepThreads) w[i] = valid ? bank[(size_t)g * 729 + i] : 0.0f;
+    prep_one_kernel(w, w + 732, valid, g, prep, tid, kPrepThreads);
 }
 
 // ------------------------------------------------------------------------------------------------------ the walk

@@ -33,13 +33,22 @@ namespace {
 // K2's device code rides in K1's first launch (bbox_partial_bank_kernel).  This file is compiled with -ffp-contract=off
 // (numpy's rounding sequence, Makefile); the bank builder and the preparation are compiled with hipcc's default
 // contraction in bank.hip, and must give the same bits here: the pragma restores that default for their code only.
+#ifdef SN_CONV_TIMING   // make -B EXTRA=-DSN_CONV_TIMING; read by tools/vox_timing.py
+// per workgroup of the one-pass launch.  A tile: 0 start, 1 points in + min/max, 2 published, 3 all tags seen, 4 descriptor,
+// 5 binned, 6 end.  A rider: 0 start, 1 taps, 2 segment sums, 3 means + bank stored, 4 verdict + |w| staged, 5 maximum + terms,
+// 6 digits + sums, 7 end.
+__device__ unsigned long long g_vox_t[1024 * 8];
+#define SN_VT(k) do { if (threadIdx.x == 0) g_vox_t[(blockIdx.y * gridDim.x + blockIdx.x) % 1024 * 8 + (k)] = wall_clock64(); } while (0)
+#define SN_BT(k) SN_VT(k)
+#else
+#define SN_VT(k) do {} while (0)
+#endif
 #pragma clang fp contract(fast)
 #include "conv_prep.h"
 #include "bank_body.inc"
 #pragma clang fp contract(off)
 
 constexpr int kThreads = 256;
-static_assert(kThreads == kBankThreads, "the rider workgroups have the bank builder's thread count");
 constexpr int kMaxKeep = 16;
 #ifndef SN_OCC_THREADS
 #define SN_OCC_THREADS 512
@@ -255,10 +264,10 @@ __global__ __launch_bounds__(kThreads) void bbox_partial_bank_kernel(const doubl
                                                                      double* __restrict__ partial, int rider_rows,
                                                                      BankRider r) {
     if ((int)blockIdx.y < rider_rows) {
-        __shared__ float bank_lds[729 + 9 + 1 + 8 + 1];
+        __shared__ __align__(16) float bank_lds[kBankPrepLdsFloats];
         const int g = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
         if (g < r.nblocks)
-            geneo_bank_body<true>(bank_lds, g, threadIdx.x, r.params, r.kinds, 9, 9, 9, r.bank, r.status, r.G, r.lambdas,
+            geneo_bank_body<true>(bank_lds, g, threadIdx.x, kThreads, r.params, r.kinds, 9, 9, 9, r.bank, r.status, r.G, r.lambdas,
                                   r.order, r.last, r.lambdas_out, r.prep);
         return;
     }
@@ -698,12 +707,16 @@ constexpr int kOnePairs = 7;
 #endif
 constexpr int kOneThreads = SN_ONE_THREADS;   // [measured, C2] 1024 threads x 8 parts per tile: stage 34.1 us; 512 x 16: 35.7-36.5 (half the partial bitmaps to write and to OR)
 constexpr int kOneParts = kOccParts * kOccThreads / kOneThreads;
-#ifdef SN_CONV_TIMING   // make -B EXTRA=-DSN_CONV_TIMING; read by tools/vox_timing.py
-__device__ unsigned long long g_vox_t[1024 * 8];   // per workgroup: 0 start, 1 points in + min/max, 2 published, 3 all tags seen, 4 descriptor, 5 binned, 6 end
-#define SN_VT(k) do { if (threadIdx.x == 0) g_vox_t[(blockIdx.y * gridDim.x + blockIdx.x) % 1024 * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define SN_VT(k) do {} while (0)
-#endif
+static_assert(kOneParts >= 1 && kOneParts <= kOccParts && kOneThreads % 64 == 0,
+              "the one-pass grid: whole waves, and no more partial bitmaps per tile than the workspace holds");
+// the workspace (SN_OCC_WS_WORDS: SN_OCC_PARTS partial bitmaps + dropped counts per tile) is sized for the two-kernel form's
+// kOccParts parts of kOccThreads threads; the one-pass form regroups the same threads, so it fits whenever it divides them
+static_assert(kOneParts * kOneThreads == kOccParts * kOccThreads && kOccParts <= SN_OCC_PARTS && kOneParts * 8 <= SN_BBOX_PARTS * 6,
+              "SN_ONE_THREADS must divide a tile's threads: kOneParts partial bitmaps fit the workspace of SN_OCC_PARTS, and "
+              "the exchange slots the partial-box workspace");
+// workgroups of the one-pass kernel that gave up the box exchange and took the tile's box from the points (0 in normal use;
+// sn_voxel_onepass_giveups)
+__device__ unsigned long long g_onepass_giveups;
 constexpr unsigned long long kOneMagic = 0x5ce7e000ull << 32;
 
 template <bool kAligned>
@@ -719,11 +732,12 @@ __global__ __launch_bounds__(kOneThreads) void occ_onepass_kernel(const double* 
                                                                   double* __restrict__ bbox_out, int spin_max,
                                                                   int rider_rows, BankRider r) {
     if ((int)blockIdx.y < rider_rows) {
-        // K2 as riders (the first grid rows: dispatched first), 256 of the 512 threads build kernel g + its preparation
-        __shared__ float bank_lds[729 + 9 + 1 + 8 + 1];
+        // K2 as riders (the first grid rows: dispatched first): all the workgroup's threads build kernel g + its preparation,
+        // one tap each -- the tile workgroups queued behind a rider start when it ends, and their siblings wait for them
+        __shared__ __align__(16) float bank_lds[kBankPrepLdsFloats];
         const int g = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-        if (g < r.nblocks && threadIdx.x < kBankThreads)
-            geneo_bank_body<true>(bank_lds, g, threadIdx.x, r.params, r.kinds, 9, 9, 9, r.bank, r.status, r.G, r.lambdas,
+        if (g < r.nblocks)
+            geneo_bank_body<true>(bank_lds, g, threadIdx.x, kOneThreads, r.params, r.kinds, 9, 9, 9, r.bank, r.status, r.G, r.lambdas,
                                   r.order, r.last, r.lambdas_out, r.prep);
         return;
     }
@@ -848,6 +862,7 @@ __global__ __launch_bounds__(kOneThreads) void occ_onepass_kernel(const double* 
         }
     }
     const bool alone = __syncthreads_or(gave_up ? 1 : 0) != 0;
+    if (alone && tid == 0) atomicAdd(&g_onepass_giveups, 1ull);
     SN_VT(3);
     if (!alone) {
         // (the boxes are read with agent-scope atomic loads, issued behind the tags' loads: no stale line of an earlier
@@ -1746,6 +1761,15 @@ extern "C" int sn_grid_to_points(const void* grid, int dtype, int n0, int n1, in
     }
 #undef SN_G2P
     return sn::check_launch("sn_grid_to_points");
+}
+
+extern "C" int sn_voxel_onepass_giveups(unsigned long long* count) {
+    if (!count) return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_onepass_giveups: null pointer");
+    unsigned long long h = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&h, HIP_SYMBOL(g_onepass_giveups), sizeof(h)) != hipSuccess)
+        return sn::check_launch("sn_voxel_onepass_giveups");
+    *count = h;
+    return SN_OK;
 }
 
 #ifdef SN_CONV_TIMING
