@@ -548,7 +548,8 @@ int sn_loss_forward(const void* pred, int pred_dtype, const void* gt, int gt_dty
  * value[0] = weight * ( sum_{mask[i] >= 1} relu(-P[i]) + [with_sum] relu(-(1 - sum_{mask[i] == 2} P[i])) ),
  * grad[i] = d value / d P[i].  P [N] f32 (the packed parameter vector), mask [N] i8: 0 = not a parameter,
  * 1 = GENEO parameter (positive_regularizer), 2 = trainable convex coefficient (cvx_loss: its own relu(-phi) and the
- * relu(-(1 - sum)) of the frozen last one). */
+ * relu(-(1 - sum)) of the frozen last one).  1 <= N <= 8192 (the launch keeps 8 N bytes in LDS), here and in
+ * sn_criterion_forward; SN_ERR_UNSUPPORTED above. */
 int sn_param_penalty(const float* P, const int8_t* mask, int N, float weight, int with_sum, float* value, float* grad,
                      sn_stream_t stream);
 

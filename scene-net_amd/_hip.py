@@ -1034,12 +1034,17 @@ def criterion_backward(pred: torch.Tensor, gt: torch.Tensor, ranges: torch.Tenso
 
 @_on_tensor_device
 def loss_backward(pred: torch.Tensor, gt: torch.Tensor, ranges: torch.Tensor, coef: torch.Tensor,
-                  upstream: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  upstream: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dL/dpred (pred's dtype and shape) from the coefficients of loss_forward (sn_loss_backward_u); upstream: a
-    one-element f64 or f32 tensor (or None = 1)."""
+    one-element f64 or f32 tensor (or None = 1); out: a contiguous tensor like pred to write into (default: a new one)."""
     B = int(pred.shape[0])
     n_per = pred.numel() // max(B, 1)
-    grad = torch.empty_like(pred)
+    if out is None:
+        grad = torch.empty_like(pred)
+    else:
+        if out.shape != pred.shape or out.dtype != pred.dtype or out.device != pred.device or not out.is_contiguous():
+            raise HipLibraryError("loss_backward: out must be contiguous with pred's shape, dtype and device")
+        grad = out
     if upstream is not None and upstream.dtype not in (torch.float64, torch.float32):
         upstream = upstream.to(torch.float64)
     up_dt = _DT[upstream.dtype] if upstream is not None else SN_F64

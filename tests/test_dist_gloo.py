@@ -3,6 +3,7 @@ job time (max over ranks) and the job total (sum), exactly as bench.py does over
 import os
 import socket
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -61,7 +62,9 @@ def _grad_worker(rank, world, port, q):
         p.grad = torch.full_like(p, float((rank + 1) * (i + 1)))
     views = [p.grad for p in params]   # the exchange writes in place
     n = sna.allreduce_flat_grads(params + [frozen])
-    q.put((rank, n, [g.clone() for g in views], frozen.grad is None))
+    # by value (numpy), not as tensors: a tensor travels as a handle to shared memory that the parent can only open while
+    # this process is alive, and it exits right after the put
+    q.put((rank, n, [g.numpy().copy() for g in views], frozen.grad is None))
     dist.destroy_process_group()
 
 
@@ -81,7 +84,8 @@ def test_two_rank_flat_gradient_exchange():
     for rank, n, grads, frozen_untouched in res:
         assert n == 7 + 5 and frozen_untouched
         for i, g in enumerate(grads):
-            assert torch.equal(g, torch.full_like(g, 1.5 * (i + 1)))   # mean of (i+1) and 2 (i+1)
+            assert g.dtype == np.float32 and g.shape == (() if i < 7 else (5,))
+            assert np.array_equal(g, np.full(g.shape, 1.5 * (i + 1), dtype=np.float32))   # mean of (i+1) and 2 (i+1)
 
 
 def test_flat_gradient_exchange_without_group_is_a_no_op():

@@ -16,6 +16,7 @@ import torch
 import scene_net_amd as sna
 from scene_net_amd import _hip
 from oracle import loss_oracle as lo
+import loss_cases as lc
 
 pytestmark = pytest.mark.gpu
 
@@ -107,42 +108,20 @@ def test_weight_target_matches_reference(hip_device, name):
     assert (w.cpu() - ref).abs().max().item() <= 2e-6 * ref.abs().max().item()  # mean over n elements in fp32
 
 
-FREQS = [3_000_000, 1200, 800, 700, 650, 400, 300, 310, 150, 9000]
-
-
-@pytest.mark.parametrize("pred_dt,gt_dt", [(torch.float32, torch.bool), (torch.float32, torch.uint8),
-                                           (torch.float32, torch.float32), (torch.float64, torch.float64),
-                                           (torch.float32, torch.float64), (torch.float64, torch.float32)])
+@pytest.mark.parametrize("pred_dt,gt_dt", lc.DTYPE_PAIRS)
 @pytest.mark.parametrize("shape", [(4, 1, 64, 64, 64), (3, 1, 7, 9, 11), (1, 1, 5, 3, 3), (2, 4099)])
 def test_against_oracle_all_dtypes_and_ragged_shapes(hip_device, pred_dt, gt_dt, shape):
-    g = torch.Generator().manual_seed(sum(shape))
-    u = torch.rand(shape, generator=g, dtype=torch.float64)
-    if gt_dt in (torch.bool, torch.uint8):
-        gt = (u < 0.05).to(gt_dt)
-    else:
-        gt = torch.where(u < 0.9, torch.zeros_like(u), torch.where(u < 0.95, torch.ones_like(u), (u - 0.95) * 20)).to(gt_dt)
-    pred = torch.rand(shape, generator=g, dtype=torch.float64).to(pred_dt)
-    freqs = torch.tensor(FREQS)
-    ranges = torch.linspace(0, 1, 11)[:-1]
-    hp = dict(alpha=1.5, eps=0.05, mse_weight=2.0)
+    pred, gt = lc.seeded_inputs(shape, pred_dt, gt_dt)
     # oracle in fp64 on the same values (gt binning happens in gt's own dtype, as the reference would)
-    po = pred.detach().clone().double().requires_grad_(True)
-    gto = gt.to(torch.float32 if gt_dt in (torch.bool, torch.uint8) else gt_dt)
-    w = lo.weight_target(gto, freqs, ranges, hp["alpha"], hp["eps"]).double()
-    ref = torch.mean(hp["mse_weight"] * w * (gto.double() - po) ** 2) + \
-        lo.focal_tversky_loss(po, gto.double(), 0.3, 0.7, 2.0, 0.5)
-    ref.backward()
-    crit = sna.GENEO_Tversky_Loss(targets=torch.zeros(4), weighting_scheme_path=None, save_weighting_scheme=False,
-                                  weight_alpha=hp["alpha"], weight_epsilon=hp["eps"], mse_weight=hp["mse_weight"],
-                                  tversky_alpha=0.3, tversky_beta=0.7, focal_gamma=2.0, tversky_smooth=0.5)
-    crit.freqs = freqs.to(hip_device)
+    ref, gref = lc.tversky_oracle(pred, gt)
+    crit = lc.tversky_criterion(hip_device)
     pd = pred.to(hip_device).requires_grad_(True)
     loss = crit(pd, gt.to(hip_device), {}, {})
     loss.backward()
-    tol = 5e-6 if pred_dt == torch.float32 else 1e-6   # oracle weights' mean is an fp32 reduction
-    assert abs(loss.item() - ref.item()) <= tol * abs(ref.item()), (loss.item(), ref.item())
-    err = (pd.grad.cpu().double() - po.grad).abs().max().item()
-    assert err <= tol * po.grad.abs().max().item(), (err, po.grad.abs().max().item())
+    tol = lc.oracle_tol(pred_dt)   # oracle weights' mean is an fp32 reduction
+    assert abs(loss.item() - ref) <= tol * abs(ref), (loss.item(), ref)
+    err = (pd.grad.cpu().double() - gref).abs().max().item()
+    assert err <= tol * gref.abs().max().item(), (err, gref.abs().max().item())
 
 
 def test_full_size_properties(hip_device):

@@ -365,3 +365,46 @@ def test_tracked_parameters_stay_ordinary_parameters():
             q.grad = torch.ones_like(q)
     opt.step()
     assert sn._DATA_TOUCHES[0] == t1                                    # optimiser steps do not go through .data
+
+
+def test_loss_plan_table_reaches_every_plan_class():
+    """The launch plan of K5 restated in tests/loss_cases.py (SN_LOSS_PARTS of include/scenenet_hip.h; span_of and the
+    backward part count, loss.hip:540-544 and :656) against the text it restates, and the sizes the GPU tests run
+    (tests/test_gpu_loss_plans.py): on both passes they reach one part, several parts split exactly and unevenly (the last
+    part is shorter) and the capped count split exactly and unevenly, in the vector loop (n_per % 4 == 0) and -- a span is a
+    multiple of 4, so no split of it is exact -- in the element loop."""
+    import re
+    import loss_cases as lc
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "scenenet_hip.h")) as f:
+        assert ("#define SN_LOSS_PARTS(n_per) ((n_per) <= 16384 ? 1 : ((n_per) >= 16384 * 256 ? 256 : "
+                "(int)(((n_per) + 16383) / 16384)))") in f.read()
+    with open(os.path.join(root, "scene-net_amd", "csrc", "loss.hip")) as f:
+        src = f.read()
+    assert "n_per <= 8192 ? 1 : (n_per >= 8192L * 512 ? 512 : (int)((n_per + 8191) / 8192))" in src
+    assert re.search(r"long s = \(long\)\(\(n_per \+ nparts - 1\) / nparts\);\s*return \(s \+ 3\) / 4 \* 4;", src)
+    want = {  # n_per: (forward parts, forward span, backward parts, backward span, vector loop)
+        8191: (1, 8192, 1, 8192, False), 8192: (1, 8192, 1, 8192, True), 8193: (1, 8196, 2, 4100, False), 8196: (1, 8196, 2, 4100, True),
+        16384: (1, 16384, 2, 8192, True), 16385: (2, 8196, 3, 5464, False), 16388: (2, 8196, 3, 5464, True),
+        32768: (2, 16384, 4, 8192, True), 4_194_304: (256, 16384, 512, 8192, True),
+        4_194_307: (256, 16388, 512, 8196, False), 4_194_308: (256, 16388, 512, 8196, True),
+        6_000_001: (256, 23440, 512, 11720, False)}
+    sizes = lc.SMALL_N + lc.LARGE_N
+    assert sorted(sizes) == sorted(want)
+    reached = {"forward": set(), "backward": set()}
+    for n in sizes:
+        assert lc.plan(n) == want[n], n
+        assert _hip.loss_parts(n) == want[n][0]
+        fp, fs, bp, bs, vec = lc.plan(n)
+        for which, parts, span, cap in (("forward", fp, fs, lc.FWD_CAP), ("backward", bp, bs, lc.BWD_CAP)):
+            bounds = lc.part_bounds(n, parts, span)
+            assert bounds[0][0] == 0 and bounds[-1][1] == n and span % 4 == 0
+            assert all(a[1] == b[0] and a[0] < a[1] for a, b in zip(bounds, bounds[1:])) and bounds[-1][0] < n
+            last = bounds[-1][1] - bounds[-1][0]
+            kind = "one" if parts == 1 else ("capped" if parts == cap else "several") + (" exact" if last == span else " uneven")
+            reached[which].add((kind, vec))
+    # the last parts the issue names: 8196 backward, 16388 on both passes, 4 194 308 forward
+    assert 8196 - 4100 == 4096 and 16388 - 8196 == 8192 and 16388 - 2 * 5464 == 5460 and 4_194_308 - 255 * 16388 == 15368
+    need = {("one", True), ("one", False), ("several exact", True), ("several uneven", True), ("several uneven", False),
+            ("capped exact", True), ("capped uneven", True), ("capped uneven", False)}
+    assert reached["forward"] >= need and reached["backward"] >= need, reached
