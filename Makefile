@@ -14,7 +14,7 @@ FLAGS_voxel := -ffp-contract=off
 # metrics.hip: the fp64 value arithmetic is metrics.py's binary_metric_values operation for operation
 FLAGS_metrics := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

@@ -640,6 +640,28 @@ int sn_binary_curve(const void* pred, int pred_dtype, const void* target, int ta
                     uint64_t* batch, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K7 -- tile ingest: the raw rows of a batch of tiles -> the pts / labels layout of K1 and sn_gather_points.
+ * replaces: the per-sample split on the host, core/datasets/ts40k.py:201-207 (`npy = np.load(...)`,
+ *           `sample = (npy[:, 0:-1], npy[:, -1])`; tiles.split_tile + pack_csr here): a file's rows go host-to-device
+ *           as they are and are de-interleaved on the device.
+ * ------------------------------------------------------------------------- */
+
+/* rows [total, cols] row-major of row_dtype (SN_F64 | SN_F32): the raw rows of B tiles, concatenated (element-aligned).
+ * pts [total,3] f64 = columns 0..2; labels (nullable) [total] f64 = column cols-1.  3 <= cols <= 8; labels need cols >= 4.
+ * f64 rows: every 64-bit pattern is carried unchanged (NaN payloads, -0.0, denormals).  f32 rows: the exact widening (a
+ * NaN keeps sign and payload and gets the quiet bit).  Nothing beyond `total` is written.  With cols == 4 and rows, pts,
+ * labels 16-byte aligned the kernel moves two points per lane with 16-byte accesses; otherwise one point per lane.
+ * bad (nullable) [B] i32, WRITTEN (not accumulated) by the call: points of tile b with a non-finite value in a column
+ * that is read (x, y, z; the label column only when labels is given); needs offsets [B+1] i64 (device, CSR).  offsets
+ * may be null iff bad is null.  A memset node (bad only) and one launch; integer atomics for the non-finite points only:
+ * no allocation, no synchronisation, capturable, independent of launch order.
+ * SN_ERR_INVALID_ARG: null rows / pts, total <= 0, B <= 0, cols outside 3..8, labels with cols == 3, bad without offsets,
+ * an unknown dtype, a misaligned pointer;  SN_ERR_UNSUPPORTED: a known dtype other than SN_F32 / SN_F64. */
+int sn_tiles_unpack(const void* rows, int row_dtype, int cols, int64_t total, const int64_t* offsets, int B,
+                    double* pts, double* labels, int32_t* bad, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,7 @@ SYMBOLS = {
     "sn_binary_stats": (c_int, [_P, _I, _P, _I, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
     "sn_binary_curve_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I, _I]),
     "sn_binary_curve": (c_int, [_P, _I, _P, _I, ctypes.c_int64, _I, _P, _I, _P, ctypes.c_size_t, _P, _P, _P]),
+    "sn_tiles_unpack": (c_int, [_P, _I, _I, ctypes.c_int64, _P, _I, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -1141,3 +1142,30 @@ def binary_curve(pred: torch.Tensor, target: torch.Tensor, thresholds, ws: torch
                                 _ptr(ws, None, "ws"), ws.numel() * ws.element_size(), _ptr(state, torch.int64, "state"),
                                 _ptr(batch, torch.int64, "batch"), _stream())
     _check(rc, "sn_binary_curve")
+
+
+# --------------------------------------------------------------------------- #
+@_on_tensor_device
+def tiles_unpack(rows: torch.Tensor, pts: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                 offsets: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None) -> None:
+    """sn_tiles_unpack: rows [total, cols] (f64 | f32, the raw rows of the batch's tiles, concatenated) -> pts[:total]
+    (columns 0..2) and labels[:total] (the last column), both f64 and written in place: pts holds at least total x 3
+    and labels at least total elements, and nothing beyond `total` is touched.  bad [B] i32 (with offsets [B+1] i64) is
+    overwritten with every tile's count of points that carry a non-finite value in a column that is read.  Allocates
+    nothing and does not synchronise."""
+    if rows.dim() != 2:
+        raise HipLibraryError(f"rows must be [total, cols] (got {tuple(rows.shape)})")
+    if rows.dtype not in (torch.float64, torch.float32):
+        raise HipLibraryError(f"rows must be float64 or float32 (got {rows.dtype})")
+    total, cols = int(rows.shape[0]), int(rows.shape[1])
+    if pts.numel() < 3 * total or (labels is not None and labels.numel() < total):
+        raise HipLibraryError("pts / labels are smaller than the rows they are to hold")
+    B = 1
+    if offsets is not None:
+        B = int(offsets.numel()) - 1
+        if bad is not None and bad.numel() < B:
+            raise HipLibraryError("bad must hold one count per tile")
+    rc = load().sn_tiles_unpack(_ptr(rows, None, "rows"), _DT[rows.dtype], cols, total,
+                                _ptr(offsets, torch.int64, "offsets"), B, _ptr(pts, torch.float64, "pts"),
+                                _ptr(labels, torch.float64, "labels"), _ptr(bad, torch.int32, "bad"), _stream())
+    _check(rc, "sn_tiles_unpack")
