@@ -13,8 +13,10 @@ CXXFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(SRC) -Wall
 FLAGS_voxel := -ffp-contract=off
 # metrics.hip: the fp64 value arithmetic is metrics.py's binary_metric_values operation for operation
 FLAGS_metrics := -ffp-contract=off
+# towers.hip: the stencil's fp64 inclusion test is evaluated in exactly the documented form
+FLAGS_towers := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

@@ -23,6 +23,7 @@
 #ifndef SCENENET_HIP_H
 #define SCENENET_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -660,6 +661,64 @@ int sn_binary_curve(const void* pred, int pred_dtype, const void* target, int ta
  * an unknown dtype, a misaligned pointer;  SN_ERR_UNSUPPORTED: a known dtype other than SN_F32 / SN_F64. */
 int sn_tiles_unpack(const void* rows, int row_dtype, int cols, int64_t total, const int64_t* offsets, int B,
                     double* pts, double* labels, int32_t* bad, sn_stream_t stream);
+
+
+/* ------------------------------------------------------------------------- *
+ * K8 -- tower proposals: DBSCAN over the voxels of a thresholded prediction, on the device.
+ * replaces: eda.extract_towers (utils/pcd_processing.py:577-651: open3d's cluster_dbscan and a pandas group-by, one tile
+ *           at a time on the host) behind prob_to_label (utils/voxelization.py:304-323) and vxg_to_xyz, as extract_towers,
+ *           compute_euc_dists and get_tower_proposals call it with eps = 3.5, min_points = 18
+ *           (utils/observer_utils.py:397-473, 556-); the statistics rows carry what filter_towers (:503-549) and
+ *           aggregate_centroids (:476-500) read from the clusters.
+ *
+ * grid [B, n0, n1, n2] (the project's grids are [.., nz, nx, ny]: axis 0 is z); tiles are independent.
+ *   positive: grid >= tau in the grid's own dtype (tau rounded to it as sn_binary_stats rounds it); NaN is not positive;
+ *             SN_U8 / SN_OCC8: non-zero, tau ignored
+ *   stencil:  the offsets (d0, d1, d2) with (d0 s0)^2 + (d1 s1)^2 + (d2 s2)^2 <= eps^2, in fp64 in exactly this form,
+ *             s = voxel_size per grid axis (null: 1, 1, 1); inclusive; (0, 0, 0) belongs to it; at most 10 voxels per axis
+ *   core:     positive, and at least min_points positives of its own tile inside its stencil (clipped at the grid faces)
+ *   cluster:  a connected component of the cores under stencil adjacency; ids 0..K-1 ascend with each cluster's smallest
+ *             core voxel (linear index in memory order)
+ *   border:   positive, not core, a core inside its stencil: takes the smallest id among those cores
+ *   labels:   the id, -1 for everything else
+ * ------------------------------------------------------------------------- */
+#define SN_TOWER_NSTAT 12   /* n_voxels, n_core, sum_i0, sum_i1, sum_i2, min_i0, min_i1, min_i2, max_i0, max_i1, max_i2, first_core_index */
+#define SN_TOWER_LAUNCHES 6 /* threshold, core, union, flatten, rank, finish */
+
+/* The stencil's rows: rows_host [cap, 3] receives (d0, d1, half-width along axis 2) of the first `cap` rows, ascending in
+ * (d0, d1) (null: none); n_offsets (nullable) the number of offsets, sum of 2 * half-width + 1.  Host only, no GPU.
+ * Returns the row count (>= 1); SN_ERR_INVALID_ARG for eps or a voxel size that is not positive and finite;
+ * SN_ERR_UNSUPPORTED when eps reaches more than 10 voxels along an axis. */
+int sn_towers_stencil(double eps, const double* voxel_size_host, int32_t* rows_host, int cap, int64_t* n_offsets);
+
+/* Workspace bytes of one sn_tower_proposals call: 0 for a shape the entry refuses (an extent <= 0, more than 2^24 voxels
+ * per tile or 2^36 per call, rows counted as padded to a multiple of 64; more than 65535 tiles). */
+size_t sn_towers_ws_bytes(int B, int n0, int n1, int n2);
+
+/* grid: SN_F32 | SN_BF16 | SN_F64 | SN_U8 | SN_OCC8, element-aligned.  tau in (0, 1) for the float dtypes; eps > 0 and
+ * finite; voxel_size_host: 3 doubles in HOST memory or null, read during the call only (the stencil travels as a kernel
+ * argument: a captured replay keeps that of capture time); min_points >= 1; max_towers >= 0.
+ * ws: caller-owned scratch of ws_bytes >= sn_towers_ws_bytes(...), 8-byte aligned.
+ * labels [B, n0, n1, n2] i32: always the full ids.  n_towers [B] i32: the true K, also when K > max_towers.
+ * stats [B, max_towers, SN_TOWER_NSTAT] i64 (null iff max_towers == 0): rows of the ids below max_towers, over every
+ * voxel that carries the id (cores and borders; n_core counts the cores); rows of absent clusters are zero.
+ * SN_TOWER_LAUNCHES launches on `stream`; lock-free union-find (compare-and-swap on parents that only decrease), no
+ * workgroup waits for another; integer atomics only: results do not depend on scheduling.  No allocation, no
+ * synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null pointer, B or an extent <= 0, min_points < 1, eps <= 0 or not finite, tau outside (0, 1)
+ * for a float grid, max_towers < 0, a short workspace, a misaligned pointer, an unknown dtype;  SN_ERR_UNSUPPORTED: a known
+ * dtype that is no grid dtype (SN_I32), eps beyond 10 voxels along an axis, a shape sn_towers_ws_bytes refuses. */
+int sn_tower_proposals(const void* grid, int dtype, int B, int n0, int n1, int n2, double tau, double eps,
+                       const double* voxel_size_host, int min_points, int max_towers, void* ws, size_t ws_bytes,
+                       int32_t* labels, int32_t* n_towers, int64_t* stats, sn_stream_t stream);
+
+/* DIAGNOSTIC entry, no part of the stable interface: the launches first..last (1-based, of SN_TOWER_LAUNCHES) of the same
+ * call and nothing else.  tools/towers_bench.py times the prefixes 1..k through it and takes differences.  The number
+ * and order of the launches may change with the kernels; launches left out must have run before on the same workspace. */
+int sn_tower_proposals_launches(const void* grid, int dtype, int B, int n0, int n1, int n2, double tau, double eps,
+                                const double* voxel_size_host, int min_points, int max_towers, void* ws, size_t ws_bytes,
+                                int32_t* labels, int32_t* n_towers, int64_t* stats, int first, int last,
+                                sn_stream_t stream);
 
 
 #ifdef __cplusplus

@@ -96,6 +96,12 @@ SYMBOLS = {
     "sn_binary_curve_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I, _I]),
     "sn_binary_curve": (c_int, [_P, _I, _P, _I, ctypes.c_int64, _I, _P, _I, _P, ctypes.c_size_t, _P, _P, _P]),
     "sn_tiles_unpack": (c_int, [_P, _I, _I, ctypes.c_int64, _P, _I, _P, _P, _P, _P]),
+    "sn_towers_stencil": (c_int, [ctypes.c_double, _P, _P, _I, _P]),
+    "sn_towers_ws_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
+    "sn_tower_proposals": (c_int, [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _I, _I, _P,
+                                   ctypes.c_size_t, _P, _P, _P, _P]),
+    "sn_tower_proposals_launches": (c_int, [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _I, _I, _P,
+                                            ctypes.c_size_t, _P, _P, _P, _I, _I, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -105,6 +111,7 @@ SN_BBOX_PARTS = 32
 SN_METRIC_NCOUNT, SN_METRIC_NVALUE, SN_METRIC_MAX_PARTS = 6, 5, 1024
 SN_METRIC_WS_BYTES = SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8
 SN_CURVE_MAX_THRESHOLDS = 255
+SN_TOWER_NSTAT, SN_TOWER_LAUNCHES, SN_TOWER_MAX_RADIUS = 12, 6, 10
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1169,3 +1176,67 @@ def tiles_unpack(rows: torch.Tensor, pts: torch.Tensor, labels: Optional[torch.T
                                 _ptr(offsets, torch.int64, "offsets"), B, _ptr(pts, torch.float64, "pts"),
                                 _ptr(labels, torch.float64, "labels"), _ptr(bad, torch.int32, "bad"), _stream())
     _check(rc, "sn_tiles_unpack")
+
+
+# --------------------------------------------------------------------------- #
+_TOWER_DT = {torch.float32: SN_F32, torch.bfloat16: SN_BF16, torch.float64: SN_F64, torch.uint8: SN_U8, torch.bool: SN_OCC8}
+
+
+def _voxel_size_c(voxel_size):
+    if voxel_size is None:
+        return None
+    vs = [float(v) for v in voxel_size]
+    if len(vs) != 3:
+        raise ValueError("voxel_size must have 3 entries, one per grid axis")
+    return (ctypes.c_double * 3)(*vs)
+
+
+def towers_stencil(eps: float, voxel_size=None):
+    """sn_towers_stencil (host only): (rows [R, 3] int32 = d0, d1, half-width along axis 2; number of offsets)."""
+    vs = _voxel_size_c(voxel_size)
+    cap = (2 * SN_TOWER_MAX_RADIUS + 1) ** 2
+    rows = (ctypes.c_int32 * (3 * cap))()
+    n = ctypes.c_int64(0)
+    rc = load().sn_towers_stencil(float(eps), ctypes.cast(vs, c_void_p) if vs is not None else None,
+                                  ctypes.cast(rows, c_void_p), cap, ctypes.cast(ctypes.pointer(n), c_void_p))
+    if rc < 0:
+        _check(rc, "sn_towers_stencil")
+    return torch.tensor(list(rows[:3 * rc]), dtype=torch.int32).reshape(rc, 3), int(n.value)
+
+
+def towers_ws_bytes(B: int, n0: int, n1: int, n2: int) -> int:
+    """sn_towers_ws_bytes: scratch bytes of one tower_proposals call (host only)."""
+    need = int(load().sn_towers_ws_bytes(int(B), int(n0), int(n1), int(n2)))
+    if need == 0:
+        raise HipLibraryError(f"sn_tower_proposals serves no grid of {B} x ({n0}, {n1}, {n2}) (positive extents, at most "
+                              "2^24 voxels per tile with rows padded to 64)")
+    return need
+
+
+@_on_tensor_device
+def tower_proposals(grid: torch.Tensor, tau: float, eps: float, min_points: int, max_towers: int, ws: torch.Tensor,
+                    labels: torch.Tensor, n_towers: torch.Tensor, stats: Optional[torch.Tensor], voxel_size=None,
+                    launches: Optional[Tuple[int, int]] = None) -> None:
+    """sn_tower_proposals over grid [B, n0, n1, n2] (f32 | bf16 | f64 | u8 | bool): labels [B, n0, n1, n2] i32, n_towers
+    [B] i32, stats [B, max_towers, SN_TOWER_NSTAT] i64, all caller-owned like the scratch `ws`
+    (towers_ws_bytes).  voxel_size: 3 floats or a ctypes array built once.  launches = (first, last): only those of the
+    SN_TOWER_LAUNCHES launches (sn_tower_proposals_launches: timing).  No allocation, no synchronisation."""
+    if grid.dim() != 4:
+        raise HipLibraryError(f"grid must be [B, n0, n1, n2] (got {tuple(grid.shape)})")
+    if grid.dtype not in _TOWER_DT:
+        raise HipLibraryError(f"grid must be float32, bfloat16, float64, uint8 or bool (got {grid.dtype})")
+    B, n0, n1, n2 = (int(v) for v in grid.shape)
+    max_towers = int(max_towers)
+    if labels.numel() != grid.numel() or n_towers.numel() != B or \
+            (stats is not None and stats.numel() != B * max_towers * SN_TOWER_NSTAT):
+        raise HipLibraryError("labels / n_towers / stats do not have the sizes of this grid and max_towers")
+    vs = voxel_size if isinstance(voxel_size, ctypes.Array) else _voxel_size_c(voxel_size)
+    head = (_ptr(grid, None, "grid"), _TOWER_DT[grid.dtype], B, n0, n1, n2, float(tau), float(eps),
+            ctypes.cast(vs, c_void_p) if vs is not None else None, int(min_points), max_towers, _ptr(ws, None, "ws"),
+            ws.numel() * ws.element_size(), _ptr(labels, torch.int32, "labels"), _ptr(n_towers, torch.int32, "n_towers"),
+            _ptr(stats, torch.int64, "stats"))
+    if launches is None:
+        rc = load().sn_tower_proposals(*head, _stream())
+    else:
+        rc = load().sn_tower_proposals_launches(*head, int(launches[0]), int(launches[1]), _stream())
+    _check(rc, "sn_tower_proposals")

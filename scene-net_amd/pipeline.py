@@ -144,6 +144,18 @@ class ScenePipeline:
                        else _hip.conv_bank(x, bank, lam, want_act=False, want_out=True)[1])
             return self._finish(out, grids, batch, want_gt)
 
+    def tower_proposals(self, pred: torch.Tensor, grids: Optional[VoxelGrids] = None, **kw):
+        """The tower instances of a prediction of this pipeline: towers.tower_proposals(pred, ...) with `self.tau` where
+        no tau is given (what eda.extract_towers gives after prob_to_label, utils/observer_utils.py:397-473).  grids: the
+        VoxelGrids the prediction came from, kept on the result as `.grids` (its `desc` holds every tile's bounds for
+        TowerProposals.to_world)."""
+        from .towers import tower_proposals
+        if kw.get("tau") is None:
+            kw["tau"] = self.tau
+        props = tower_proposals(pred, **kw)
+        props.grids = grids   # (a declared field of TowerProposals, None from tower_proposals itself)
+        return props
+
     def capture(self, batch: PointBatch, want_gt: bool = False) -> "CapturedPipeline":
         """The whole pass over `batch` (its device buffers, as they are refilled in place later) recorded into one
         hipGraph: 7 launches replayed with one call and no dispatch gaps.  Inference only (runs under no_grad)."""
