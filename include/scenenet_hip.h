@@ -352,7 +352,11 @@ int sn_voxel_desc_from_bounds(const double* bounds, int B, int nx, int ny, int n
  *   size_xyz_host  3 doubles on the host (voxel size per axis, > 0)
  *   dims           (nullable) [B,3] i32 out: n_x, n_y, n_z of every tile
  *   status         (nullable) [B] i32 out: 1 = the tile needs more voxels than the maximum (points beyond the table
- *                  are dropped and counted by the scatter) */
+ *                  are dropped and counted by the scatter)
+ * For the scatter and the LDS-bitmap kernels a size-mode descriptor is defined only for the points it was built from
+ * (none of them is above its tile's own last edge).  They bin with the padded table as it stands: a foreign point above
+ * a tile's own last edge on an axis with n_a < the maximum lands in the padding cell n_a of that axis, is counted there
+ * and is NOT reported in `dropped`.  sn_gather_points alone treats such a point as outside (`fill`). */
 int sn_voxel_desc_sized(const double* bbox, int B, const double* size_xyz_host, int nx, int ny, int nz,
                         double* desc, int32_t* dims, int32_t* status, sn_stream_t stream);
 
@@ -365,7 +369,11 @@ int sn_voxel_finalize_sized(const int32_t* counts, const int32_t* tower_counts, 
 /* Atomic scatter: counts[b,z,x,y] += 1 per point; tower_counts (nullable) += 1
  * per point whose label equals one of keep_labels_host[0..n_keep) (<= 16).
  * Both grids [B,nz,nx,ny] i32 are zeroed by the call.
- * dropped (nullable) [B] i32: points that fall outside the edge table. */
+ * The binning rule, for ANY point (the descriptor need not come from these points -- a fixed box, a crop's grid): per
+ * axis the index is np.clip(np.searchsorted(edges, p, side="left") - 1, 0, n), i.e. the largest j with edges[j] < p.  A
+ * point at or below the first edge (-inf included) is clipped into bin 0 and counted there; index n on any axis -- a
+ * point above the last edge, +inf -- or a NaN coordinate means outside the table: the point is counted in no voxel.
+ * dropped (nullable) [B] i32: the points outside the edge table, each once; counts.sum() + dropped == the tile's points. */
 int sn_voxel_scatter(const double* pts, const double* labels, const int64_t* offsets, int B,
                      const double* desc, int nx, int ny, int nz,
                      int32_t* counts, int32_t* tower_counts,
@@ -393,7 +401,9 @@ int sn_voxel_finalize(const int32_t* counts, const int32_t* tower_counts, int B,
  *               (where ToFullDense(density) != (count > 0)); such tiles are recomputed exactly (counts by
  *               global atomics, column minima) by one gated launch when counts_ws (and towers_ws with
  *               gt_occ) is given: counts_ws, towers_ws [B,nz,nx,ny] i32 scratch (nullable).
- *   dropped     (nullable) [B] i32: points outside the edge table. */
+ *   dropped     (nullable) [B] i32: points outside the edge table, each once however many z-slabs the bitmap takes.
+ * Binning rule as sn_voxel_scatter's, for any point: below the first edge -> bin 0; above the last edge, +inf or NaN ->
+ * outside (sets no bit, counted in dropped) -- in the bitmap kernels and in the exact recomputation alike. */
 #define SN_OCC_PARTS 16
 #define SN_OCC_WS_WORDS(B, V, planes) ((size_t)(B) * SN_OCC_PARTS * ((planes) * ((V) / 32) + 1))
 int sn_voxel_occupancy(const double* pts, const double* labels, const int64_t* offsets, int B,
@@ -452,8 +462,13 @@ int sn_voxel_occupancy_sized_bank(const double* pts, const double* labels, const
 
 
 /* Grid -> points: out[c, i] = grid[b(i), c, vz, vx, vy] for every point i of the batch, binned exactly as the
- * scatter binned it (same desc); points outside the edge table get `fill`.  grid [B,channels,nz,nx,ny] and
- * out [channels, total] are of `dtype` (SN_F32 | SN_F64).  The reference only has the voxel-list direction
+ * scatter binned it (same desc); points outside the edge table get `fill`.  The points need not be the ones the
+ * descriptor was built from (labelling a full cloud from the grid of a crop): the rule is sn_voxel_scatter's -- at or
+ * below the first edge of an axis (-inf included) -> bin 0; above the last edge, +inf or NaN -> outside -> `fill` (any
+ * value, NaN included).  With a size-mode descriptor the last edge is the tile's OWN (edge n_a, the last finite one):
+ * the +inf padding beyond it is not part of the tile's grid.  grid [B,channels,nz,nx,ny] and out [channels, total] are
+ * of `dtype` (SN_F32 | SN_F64); total = offsets[B] is the channel stride of `out`, so `pts` holds exactly that many
+ * points as far as `out` is concerned; desc is [B, SN_DESC_LEN(nx,ny,nz)].  The reference only has the voxel-list direction
  * (vxg_to_xyz, utils/voxelization.py:328-360) and prob_to_label (:304-323); per-point read-back of the
  * prediction (BASELINE config 4) is defined here. */
 int sn_gather_points(const void* grid, int dtype, int channels, const double* pts, const int64_t* offsets, int B,

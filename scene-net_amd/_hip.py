@@ -859,10 +859,20 @@ def voxel_occupancy_sized(pts, labels, offsets, size_xyz: Sequence[float], n_xyz
 @_on_tensor_device
 def gather_points(grid: torch.Tensor, pts: torch.Tensor, offsets: torch.Tensor, desc: torch.Tensor,
                   fill: float = 0.0) -> torch.Tensor:
-    """grid [B,C,nz,nx,ny] (f32|f64) -> per-point values [C, total] via the scatter's binning (sn_gather_points)."""
+    """grid [B,C,nz,nx,ny] (f32|f64) -> per-point values [C, total] via the scatter's binning (sn_gather_points).
+    pts must hold exactly the batch's offsets[B] points: the kernel strides the channels of `out` by offsets[B] (a device
+    value), this wrapper allocates them pts.shape[0] apart."""
     if grid.dim() != 5 or grid.dtype not in (torch.float32, torch.float64):
         raise HipLibraryError("grid must be [B,C,nz,nx,ny] float32/float64")
     B, C, nz, nx, ny = grid.shape
+    # host-side shape checks, no synchronisation: the kernel reads desc[b * desc_len + ..] and offsets[0..B] unchecked
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [N,3] (got {tuple(pts.shape)})")
+    if offsets.numel() != B + 1:
+        raise HipLibraryError(f"offsets must have B + 1 = {B + 1} entries for a grid of {B} tiles (got {offsets.numel()})")
+    if tuple(desc.shape) != (B, desc_len(nx, ny, nz)):
+        raise HipLibraryError(f"desc must be [B, desc_len(nx, ny, nz)] = [{B}, {desc_len(nx, ny, nz)}] "
+                              f"(got {tuple(desc.shape)})")
     out = torch.empty((C, pts.shape[0]), dtype=grid.dtype, device=grid.device)
     rc = load().sn_gather_points(_ptr(grid, None, "grid"), _DT[grid.dtype], C, _ptr(pts, torch.float64, "pts"),
                                  _ptr(offsets, torch.int64, "offsets"), B, _ptr(desc, torch.float64, "desc"),

@@ -353,9 +353,10 @@ __global__ void desc_kernel(const double* __restrict__ box, int nparts, int nx, 
 // is cubed, every axis is then extended by m = ((range // size) + 1) * size - range (range = the ORIGINAL extent of
 // that axis) and gets n = int((max - min) / size) voxels -- n is data dependent, so a batch is voxelised into grids of
 // a caller-given maximum (nx, ny, nz) and the descriptor carries each tile's own table: edges 0..n_a are
-// numpy.linspace(lo, hi, n_a + 1) bit for bit, edges beyond are +inf (no point is ever above them, so the binning,
-// scatter and gather kernels run unchanged on the padded table; a row / column of the grid is REAL iff its upper edge
-// is finite).  dims (nullable) [B,3] i32 receives (n_x, n_y, n_z); status (nullable) [B] i32 is 1 where a tile needs
+// numpy.linspace(lo, hi, n_a + 1) bit for bit, edges beyond are +inf (none of the tile's OWN points is above edge n_a, so
+// the binning and scatter kernels run unchanged on the padded table; a row / column of the grid is REAL iff its upper
+// edge is finite -- a FOREIGN point above edge n_a bins into the padding cell n_a, which only gather_points_kernel
+// rejects).  dims (nullable) [B,3] i32 receives (n_x, n_y, n_z); status (nullable) [B] i32 is 1 where a tile needs
 // more voxels than the maximum (its points beyond the table are dropped and counted in `dropped`).
 struct Vec3s { double v[3]; };
 // numpy's floor_divide for positive doubles (npy_divmod): fmod is exact, the quotient of (a - mod) by b is rounded to
@@ -1240,7 +1241,8 @@ __global__ __launch_bounds__(kThreads) void finalize_kernel(const int32_t* __res
 
 // ---------------------------------------------------------------- grid -> points (per-point gather)
 // out[i] = grid[b, vz(i), vx(i), vy(i)] with the SAME binning as the scatter (so a point reads the voxel it fell
-// into); points outside the edge table get `fill`.
+// into); points outside the edge table (NaN, above the last edge of an axis -- a size-mode tile's OWN last edge) get
+// `fill`; points at or below the first edge read bin 0, as np.clip(np.searchsorted(e, p) - 1, 0, n) has it.
 // vxg_to_xyz: one thread per cell, one 32-byte row (two 16-byte stores; a wave writes 2 KB contiguous)
 struct Vec3d { double v[3]; };
 template <typename T>
@@ -1271,9 +1273,18 @@ __global__ __launch_bounds__(kThreads) void gather_points_kernel(const T* __rest
     const size_t V = (size_t)nx * ny * nz;
     const T* g = grid + (size_t)b * channels * V;
     const long total = offsets[gridDim.y];
+    // a size-mode table is padded with +inf edges beyond the tile's own n_a: flat() bins a point beyond the tile's own last
+    // edge into the padding cell n_a (its upper edge is +inf, so nothing is ever above it).  That cell is not part of the
+    // tile's grid: such a point is outside, like one beyond an unpadded table.  (Uniform per workgroup; n-mode skips it.)
+    const bool padded = !(bin.ex[nx] <= DBL_MAX && bin.ey[ny] <= DBL_MAX && bin.ez[nz] <= DBL_MAX);
     for_each_point<kAligned>(pts, offsets[b], offsets[b + 1], (long)blockIdx.x * kThreads + threadIdx.x,
                              (long)gridDim.x * kThreads, [&](double x, double y, double z, long i) {
-                                 const int f = bin.flat(x, y, z);
+                                 int f = bin.flat(x, y, z);
+                                 if (padded && f >= 0) {
+                                     const int r = f / ny, iy = f - r * ny, iz = r / nx, ix = r - iz * nx;
+                                     if (!(bin.ex[ix + 1] <= DBL_MAX && bin.ey[iy + 1] <= DBL_MAX && bin.ez[iz + 1] <= DBL_MAX))
+                                         f = -1;
+                                 }
                                  for (int c = 0; c < channels; ++c)
                                      out[(size_t)c * total + i] = (f < 0) ? fill : g[(size_t)c * V + f];
                              });

@@ -92,9 +92,10 @@ def batch_to_device(tiles, labels=None, device=None, stream: Optional[torch.cuda
 def point_predictions(pred: torch.Tensor, batch: PointBatch, grids: VoxelGrids, fill: float = 0.0,
                       tau: Optional[float] = None) -> torch.Tensor:
     """pred [B,C,nz,nx,ny] (f32|f64) -> [C, total_points]: every point reads the voxel it was binned into
-    (same descriptor as the scatter).  With `tau`, values are thresholded like prob_to_label
-    (utils/voxelization.py:304-323)."""
-    out = _hip.gather_points(pred.contiguous(), batch.pts, batch.offsets, grids.desc, fill)
+    (same descriptor as the scatter); a point outside the descriptor's edge table reads `fill`.  With `tau`, values are
+    thresholded like prob_to_label (utils/voxelization.py:304-323): such a point's label is `fill >= tau`, 0 for a NaN fill."""
+    # (a point buffer may be longer than the batch -- a ring slot: the kernel's channel stride is the batch's total)
+    out = _hip.gather_points(pred.contiguous(), batch.pts[:batch.total_points], batch.offsets, grids.desc, fill)
     if tau is not None:
         out = (out >= tau).to(out.dtype)
     return out
