@@ -15,8 +15,10 @@ FLAGS_voxel := -ffp-contract=off
 FLAGS_metrics := -ffp-contract=off
 # towers.hip: the stencil's fp64 inclusion test is evaluated in exactly the documented form
 FLAGS_towers := -ffp-contract=off
+# crops.hip: the disc test's fp64 products and sum are rounded once each, as numpy rounds them
+FLAGS_crops := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

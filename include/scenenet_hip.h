@@ -736,6 +736,57 @@ int sn_tower_proposals_launches(const void* grid, int dtype, int B, int n0, int 
                                 sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K9 -- scan crops: K disc / box regions cut out of one scan into a CSR batch of K tiles, on the device.
+ * replaces: the host-side crops of utils/pcd_processing.py -- crop_at_locations (:820-840), crop_tower_radius (:666-697),
+ *           crop_two_towers (:700-739) and crop_tower_samples (:805-817), which core/datasets/ts40k.py:31-148
+ *           build_data_samples drives: each an `a[mask]` over the whole cloud, once per centre.
+ *
+ * scan:     pts [n,3] f64 (x, y, z), labels [n] f64 or null -- the layout of K1 and K7
+ * regions:  regions [K,4] f64 and kinds [K] i32 (null: all discs), both on the DEVICE
+ *   SN_CROP_DISC  row (cx, cy, r, unused): point i is a member iff (x-cx)*(x-cx) + (y-cy)*(y-cy) <= r*r, evaluated in fp64
+ *                 in exactly this form, each product and the sum rounded once and never contracted -- what
+ *                 np.sum(np.power(xyz[:, :2] - c[:2], 2), axis=1) <= radius*radius computes.  z takes no part.
+ *   SN_CROP_BOX   row (xmin, ymin, xmax, ymax): a member iff xmin <= x && x <= xmax && ymin <= y && y <= ymax (inclusive on
+ *                 both ends, z disregarded: crop_two_towers)
+ *   The comparisons are taken literally: a NaN x or y is in no region; r NaN gives an empty region; a negative r behaves
+ *   as |r|; r = +inf admits every point whose dx, dy are not NaN; a box with min > max is empty; -inf <= -inf is true.
+ *   A kinds value other than 0 or 1 makes that region EMPTY (it lives in device memory: no entry can refuse it).
+ * output:   a CSR batch of K tiles.  offsets [K+1] i64 holds the TRUE sizes, whatever the capacity.  Tile k holds the
+ *           members of region k in scan order (stable): scan[mask_k] row for row.  Overlapping or repeated regions repeat
+ *           rows.  x, y, z and the label are moved as 64-bit patterns (NaN payloads, -0.0, denormals unchanged, as K7).
+ *           src [total] i64 (nullable): each output row's index in the scan.
+ * ------------------------------------------------------------------------- */
+#define SN_CROP_DISC 0
+#define SN_CROP_BOX 1
+
+/* Workspace bytes of sn_crop_count / sn_crop_scatter: 8 * K * (chunks + 1), chunks = ceil(n / sn_crops_chunk_points()).
+ * 0 for a shape the entries refuse (n <= 0, K <= 0, n > 2^36, K > 65536). */
+size_t sn_crops_ws_bytes(int64_t n, int K);
+/* Points per workgroup (1024): host only -- lets a test put its sizes on the seams. */
+int sn_crops_chunk_points(void);
+
+/* Member counts of every (region, workgroup) into ws, their exclusive prefixes per region in place, and offsets [K+1].
+ * Three launches on `stream` (count, prefix, offsets); every slot is written by exactly one workgroup: no memset, no
+ * atomics, no workgroup waits for another.  No allocation, no synchronisation: capturable; results do not depend on
+ * scheduling.
+ * SN_ERR_INVALID_ARG: a null pts / regions / ws / offsets, n <= 0, K <= 0, ws_bytes < sn_crops_ws_bytes(n, K), a
+ * misaligned pointer (8 bytes; kinds 4);  SN_ERR_UNSUPPORTED: n > 2^36 or K > 65536. */
+int sn_crop_count(const double* pts, int64_t n, const double* regions, const int32_t* kinds, int K, void* ws,
+                  size_t ws_bytes, int64_t* offsets, sn_stream_t stream);
+
+/* Called with the same pts / regions / kinds and the ws / offsets that sn_crop_count left: writes output row
+ * offsets[k] + rank of every member whose output index is < capacity -- out_pts [capacity,3], out_labels [capacity] (null
+ * iff labels is null), out_src [capacity] (nullable).  Rows at or beyond capacity and everything beyond offsets[K] are NOT
+ * touched.  The test is recomputed, for the regions whose count says the workgroup's points hold a member.  One launch;
+ * no allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: as sn_crop_count, and a null out_pts, capacity < 0, out_labels without labels or the reverse;
+ * SN_ERR_UNSUPPORTED: as sn_crop_count. */
+int sn_crop_scatter(const double* pts, const double* labels, int64_t n, const double* regions, const int32_t* kinds, int K,
+                    const void* ws, size_t ws_bytes, const int64_t* offsets, int64_t capacity, double* out_pts,
+                    double* out_labels, int64_t* out_src, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,11 @@ SYMBOLS = {
                                    ctypes.c_size_t, _P, _P, _P, _P]),
     "sn_tower_proposals_launches": (c_int, [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _I, _I, _P,
                                             ctypes.c_size_t, _P, _P, _P, _I, _I, _P]),
+    "sn_crops_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I]),
+    "sn_crops_chunk_points": (c_int, []),
+    "sn_crop_count": (c_int, [_P, ctypes.c_int64, _P, _P, _I, _P, ctypes.c_size_t, _P, _P]),
+    "sn_crop_scatter": (c_int, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P, _P,
+                                _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -112,6 +117,7 @@ SN_METRIC_NCOUNT, SN_METRIC_NVALUE, SN_METRIC_MAX_PARTS = 6, 5, 1024
 SN_METRIC_WS_BYTES = SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8
 SN_CURVE_MAX_THRESHOLDS = 255
 SN_TOWER_NSTAT, SN_TOWER_LAUNCHES, SN_TOWER_MAX_RADIUS = 12, 6, 10
+SN_CROP_DISC, SN_CROP_BOX = 0, 1
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1250,3 +1256,69 @@ def tower_proposals(grid: torch.Tensor, tau: float, eps: float, min_points: int,
     else:
         rc = load().sn_tower_proposals_launches(*head, int(launches[0]), int(launches[1]), _stream())
     _check(rc, "sn_tower_proposals")
+
+
+# --------------------------------------------------------------------------- #
+def crops_chunk_points() -> int:
+    """sn_crops_chunk_points: points per workgroup of the crop kernels (host only)."""
+    return int(load().sn_crops_chunk_points())
+
+
+def crops_ws_bytes(n: int, K: int) -> int:
+    """sn_crops_ws_bytes: scratch bytes of crop_count / crop_scatter over n points and K regions (host only)."""
+    need = int(load().sn_crops_ws_bytes(int(n), int(K)))
+    if need == 0:
+        raise HipLibraryError(f"sn_crop_count serves no scan of {n} points with {K} regions (1 <= n <= 2^36, "
+                              "1 <= K <= 65536)")
+    return need
+
+
+def _crop_head(pts, regions, kinds):
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [n, 3] (got {tuple(pts.shape)})")
+    if regions.dim() != 2 or regions.shape[1] != 4:
+        raise HipLibraryError(f"regions must be [K, 4] (got {tuple(regions.shape)})")
+    n, K = int(pts.shape[0]), int(regions.shape[0])
+    if kinds is not None and kinds.numel() != K:
+        raise HipLibraryError("kinds must hold one entry per region")
+    return n, K
+
+
+@_on_tensor_device
+def crop_count(pts: torch.Tensor, regions: torch.Tensor, kinds: Optional[torch.Tensor], ws: torch.Tensor,
+               offsets: torch.Tensor) -> None:
+    """sn_crop_count: pts [n,3] f64, regions [K,4] f64, kinds [K] i32 | None -> offsets [K+1] i64 and the per-workgroup
+    prefixes in `ws` (crops_ws_bytes), both caller-owned.  Three launches, no allocation, no synchronisation."""
+    n, K = _crop_head(pts, regions, kinds)
+    if offsets.numel() != K + 1:
+        raise HipLibraryError("offsets must hold K + 1 entries")
+    rc = load().sn_crop_count(_ptr(pts, torch.float64, "pts"), n, _ptr(regions, torch.float64, "regions"),
+                              _ptr(kinds, torch.int32, "kinds"), K, _ptr(ws, None, "ws"), ws.numel() * ws.element_size(),
+                              _ptr(offsets, torch.int64, "offsets"), _stream())
+    _check(rc, "sn_crop_count")
+
+
+@_on_tensor_device
+def crop_scatter(pts: torch.Tensor, labels: Optional[torch.Tensor], regions: torch.Tensor, kinds: Optional[torch.Tensor],
+                 ws: torch.Tensor, offsets: torch.Tensor, out_pts: torch.Tensor, out_labels: Optional[torch.Tensor],
+                 out_src: Optional[torch.Tensor], capacity: Optional[int] = None) -> None:
+    """sn_crop_scatter behind crop_count on the same arguments: fills out_pts [rows,3] f64, out_labels [rows] f64 (iff
+    labels) and out_src [rows] i64 (optional); rows at or beyond the capacity -- out_pts' row count, or a smaller
+    `capacity` -- and beyond offsets[K] are left as they are.  One launch, no allocation, no synchronisation."""
+    n, K = _crop_head(pts, regions, kinds)
+    if out_pts.dim() != 2 or out_pts.shape[1] != 3:
+        raise HipLibraryError(f"out_pts must be [capacity, 3] (got {tuple(out_pts.shape)})")
+    capacity = int(out_pts.shape[0]) if capacity is None else int(capacity)
+    if capacity > out_pts.shape[0]:
+        raise HipLibraryError("capacity exceeds the rows of out_pts")
+    if labels is not None and labels.numel() != n:
+        raise HipLibraryError("labels and pts disagree in length")
+    if (out_labels is not None and out_labels.numel() < capacity) or (out_src is not None and out_src.numel() < capacity):
+        raise HipLibraryError("out_labels / out_src are shorter than out_pts")
+    rc = load().sn_crop_scatter(_ptr(pts, torch.float64, "pts"), _ptr(labels, torch.float64, "labels"), n,
+                                _ptr(regions, torch.float64, "regions"), _ptr(kinds, torch.int32, "kinds"), K,
+                                _ptr(ws, None, "ws"), ws.numel() * ws.element_size(), _ptr(offsets, torch.int64, "offsets"),
+                                capacity, _ptr(out_pts, torch.float64, "out_pts"),
+                                _ptr(out_labels, torch.float64, "out_labels"), _ptr(out_src, torch.int64, "out_src"),
+                                _stream())
+    _check(rc, "sn_crop_scatter")

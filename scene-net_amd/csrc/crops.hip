@@ -1,0 +1,365 @@
+// K9 -- scan crops: K disc / box regions cut out of one scan into a CSR batch of K tiles (sn_crop_count, sn_crop_scatter).
+// replaces: the host-side crops of utils/pcd_processing.py -- crop_at_locations (:820-840), crop_tower_radius (:666-697),
+//           crop_two_towers (:700-739), crop_tower_samples (:805-817, driven by core/datasets/ts40k.py:31-148
+//           build_data_samples): each an `a[mask]` over the whole cloud per centre, with an np.append of the label column.
+//
+// Definition (normative, include/scenenet_hip.h): a disc row (cx, cy, r, -) holds point i iff
+// (x-cx)*(x-cx) + (y-cy)*(y-cy) <= r*r, every product and the sum rounded once in fp64 (this file is built with
+// -ffp-contract=off: a fused dx*dx + fl(dy*dy) differs from numpy's value in about one draw in eight around a UTM centre);
+// a box row (xmin, ymin, xmax, ymax) iff xmin <= x && x <= xmax && ymin <= y && y <= ymax.  The comparisons are taken
+// literally (a NaN anywhere is false).  Tile k holds region k's members in scan order; x, y, z and the label travel as
+// 64-bit patterns.
+//
+// Shape: one WAVE per workgroup and kChunk = 1024 consecutive points per workgroup -- lane l holds x, y of the points
+// chunk * 1024 + g * 64 + l, g = 0..15, in registers (64 VGPRs).  A workgroup of one wave has nobody to exchange with: no
+// LDS, no barrier.  Regions are outermost: lane l fetches row k0 + l of a tile of 64 regions with one vector load each, and
+// the row travels to the wave's scalar registers by v_readlane (a wave-uniform value per region, one fetch per 1024 points).
+// Per region and group __ballot of the membership gives the wave-uniform __popcll (count) and, in the scatter, the lane's
+// rank by mbcnt of the same mask: output order is scan order by construction, nothing depends on scheduling.
+//   count:   ws[k][chunk] = members of region k in the chunk (int64, one slot per (region, workgroup): no memset, no atomics)
+//   prefix:  one workgroup per region turns its row into exclusive prefixes, total in ws[k][nchunks]
+//   offsets: one workgroup, the exclusive prefix of the totals
+//   scatter: recomputes the test, but only for the regions whose slot says the chunk holds a member (an exact skip: the
+//            count is the count of the very same test) -- a region far from the chunk costs two loads per 64 regions.
+// Chunk-level reject in the count pass: the wave reduces its chunk's xy box (NaN coordinates left out: they are in no
+// region), every lane tests the box against ITS region of the tile (cannot_reach: conservative by construction, proof at
+// the function), and only the regions the box can reach are looped over; the others' slots get 0.
+//
+// Bound: the two passes read 24 B per point each (x, y, z share their cache lines), the scatter 8 B more per member for the
+// label and writes 32..40 B per member; per region and point 8 fp64 VALU operations.  HBM-bound up to K of a few dozen,
+// VALU-bound beyond.
+#include "common.h"
+
+namespace {
+
+constexpr int kLanes = 64;
+constexpr int kGroups = 16;                  // groups of 64 consecutive points held per lane
+constexpr int kChunk = kLanes * kGroups;     // points per workgroup
+constexpr int kMaxK = 1 << 16;
+constexpr int64_t kMaxN = (int64_t)1 << 36;  // 2^26 workgroups
+constexpr int kScanThreads = 256;
+constexpr int kScanItems = 8;                // consecutive slots per thread and step of the prefix kernel
+
+constexpr uint64_t kNaNBits = 0x7ff8000000000000ull;   // what a lane past the scan's end tests: in no region
+
+struct Region {
+    double a, b, c, d;   // disc: cx, cy, r*r, -;  box: xmin, ymin, xmax, ymax
+    int kind;            // anything but SN_CROP_DISC / SN_CROP_BOX: empty
+};
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ double readlane_f64(double v, int j) {
+    return __longlong_as_double((long long)readlane64((uint64_t)__double_as_longlong(v), j));
+}
+
+// row k of the table in the lane that asks for it; k >= K: an empty region
+__device__ __forceinline__ Region load_region(const double* __restrict__ regions, const int32_t* __restrict__ kinds, int K,
+                                              int k) {
+    Region R{0.0, 0.0, 0.0, 0.0, -1};
+    if (k < K) {
+        const double* r = regions + (int64_t)k * 4;
+        R.kind = kinds ? kinds[k] : (int)SN_CROP_DISC;
+        R.a = r[0];
+        R.b = r[1];
+        R.c = R.kind == SN_CROP_DISC ? r[2] * r[2] : r[2];   // r*r: one rounding, |r| and r alike, NaN stays NaN
+        R.d = r[3];
+    }
+    return R;
+}
+__device__ __forceinline__ Region broadcast(const Region& mine, int j) {
+    Region R;
+    R.a = readlane_f64(mine.a, j);
+    R.b = readlane_f64(mine.b, j);
+    R.c = readlane_f64(mine.c, j);
+    R.d = readlane_f64(mine.d, j);
+    R.kind = __builtin_amdgcn_readlane(mine.kind, j);
+    return R;
+}
+
+// the membership test in exactly the documented form (R.kind is wave-uniform: a scalar branch)
+__device__ __forceinline__ bool member(const Region& R, double x, double y) {
+#pragma clang fp contract(off)
+    if (R.kind == SN_CROP_DISC) {
+        const double dx = x - R.a, dy = y - R.b;
+        const double xx = dx * dx, yy = dy * dy;
+        return xx + yy <= R.c;
+    }
+    if (R.kind == SN_CROP_BOX) return R.a <= x && x <= R.c && R.b <= y && y <= R.d;
+    return false;
+}
+
+// Can no point of the xy box [xlo, xhi] x [ylo, yhi] be a member of R?  The box holds every point of the chunk whose x and y
+// are not NaN (a NaN coordinate is a member of nothing), so lo <= x <= hi for every candidate.
+// Box regions: a member has xmin <= x <= xmax, hence xhi >= x >= xmin and xlo <= x <= xmax (same for y): if one of the
+// four fails there is no member.  A NaN bound makes its comparison false: no skip.
+// Disc regions: the kernel's test is fl(fl(dx*dx) + fl(dy*dy)) <= R2 with dx = fl(x - cx), R2 = fl(r*r) -- the very R.c
+// used here.  IEEE rounding is monotone, so (1) fl(a + b) >= a for a, b >= 0 (a is representable and a + b >= a): a member
+// has fl(dx*dx) <= R2 and fl(dy*dy) <= R2;  (2) dx = fl(x - cx) is non-decreasing in x: dlo = fl(xlo - cx) <= dx <= dhi =
+// fl(xhi - cx);  (3) fl(d*d) is non-decreasing in |d|.  If dlo > 0 every |dx| >= dlo, if dhi < 0 every |dx| >= |dhi|: with
+// m that bound, fl(m*m) <= fl(dx*dx) <= R2 for a member, so fl(m*m) > R2 proves there is none.  The operations are the
+// kernel's own, rounded the same way: no margin is needed, and a point a hair beyond |r| that the rounded test admits
+// is admitted here as well.  NaN anywhere (centre, radius, inf - inf) makes the comparisons false: no skip.
+__device__ __forceinline__ bool axis_out_of_reach(double lo, double hi, double c, double r2) {
+    const double dlo = lo - c, dhi = hi - c;
+    double m;
+    if (dlo > 0.0) m = dlo;
+    else if (dhi < 0.0) m = dhi;
+    else return false;
+    return m * m > r2;
+}
+__device__ __forceinline__ bool cannot_reach(const Region& R, double xlo, double xhi, double ylo, double yhi) {
+    if (R.kind == SN_CROP_DISC) return axis_out_of_reach(xlo, xhi, R.a, R.c) || axis_out_of_reach(ylo, yhi, R.b, R.c);
+    if (R.kind == SN_CROP_BOX) return xhi < R.a || xlo > R.c || yhi < R.b || ylo > R.d;
+    return true;   // any other kind: empty
+}
+
+// smallest / largest of v over the wave, NaN left out (comparisons with a NaN are false); +inf / -inf if there is none
+__device__ __forceinline__ void wave_min_max(const uint64_t (&bits)[kGroups], double& lo, double& hi) {
+    lo = __longlong_as_double(0x7ff0000000000000ll);
+    hi = -lo;
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+        const double v = __longlong_as_double((long long)bits[g]);
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double a = __shfl_xor(lo, off, 64), b = __shfl_xor(hi, off, 64);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+}
+
+// x, y of the chunk's points as bit patterns; past the end: NaN
+__device__ __forceinline__ void load_xy(const uint64_t* __restrict__ pts, int64_t n, int64_t base, int lane,
+                                        uint64_t (&x)[kGroups], uint64_t (&y)[kGroups]) {
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+        const int64_t i = base + g * kLanes + lane;
+        const bool in = i < n;
+        x[g] = in ? pts[i * 3] : kNaNBits;
+        y[g] = in ? pts[i * 3 + 1] : kNaNBits;
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void crop_count_kernel(const uint64_t* __restrict__ pts, int64_t n,
+                                                            const double* __restrict__ regions,
+                                                            const int32_t* __restrict__ kinds, int K, int64_t nchunks,
+                                                            int64_t* __restrict__ ws) {
+    const int lane = threadIdx.x;
+    const int64_t chunk = blockIdx.x;
+    uint64_t x[kGroups], y[kGroups];
+    load_xy(pts, n, chunk * kChunk, lane, x, y);
+    double xlo, xhi, ylo, yhi;
+    wave_min_max(x, xlo, xhi);
+    wave_min_max(y, ylo, yhi);
+    for (int k0 = 0; k0 < K; k0 += kLanes) {
+        const Region mine = load_region(regions, kinds, K, k0 + lane);   // (k >= K: kind -1, out of reach)
+        unsigned long long live = __ballot(!cannot_reach(mine, xlo, xhi, ylo, yhi));
+        int mycount = 0;
+        while (live) {
+            const int j = __ffsll(live) - 1;
+            live &= live - 1;
+            const Region R = broadcast(mine, j);
+            int cnt = 0;
+#pragma unroll
+            for (int g = 0; g < kGroups; ++g)
+                cnt += __popcll(__ballot(member(R, __longlong_as_double((long long)x[g]), __longlong_as_double((long long)y[g]))));
+            if (lane == j) mycount = cnt;
+        }
+        if (k0 + lane < K) ws[(int64_t)(k0 + lane) * (nchunks + 1) + chunk] = mycount;
+    }
+}
+
+// exclusive prefix of one tile of kScanThreads * items values held `items` per thread; returns the tile's total
+template <int kItems>
+__device__ __forceinline__ int64_t block_exclusive(int64_t (&v)[kItems], int64_t* s_wave) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t sum = 0;
+#pragma unroll
+    for (int q = 0; q < kItems; ++q) {
+        const int64_t t = v[q];
+        v[q] = sum;
+        sum += t;
+    }
+    int64_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int64_t t = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int64_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kScanThreads / 64; ++w) {
+        const int64_t t = s_wave[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    __syncthreads();   // s_wave is written again by the next tile
+    const int64_t mine = before + incl - sum;
+#pragma unroll
+    for (int q = 0; q < kItems; ++q) v[q] += mine;
+    return total;
+}
+
+// workgroup k: ws[k][0 .. nchunks) counts -> exclusive prefixes, ws[k][nchunks] = the region's total
+__global__ __launch_bounds__(kScanThreads) void crop_prefix_kernel(int64_t* __restrict__ ws, int64_t nchunks) {
+    __shared__ int64_t s_wave[kScanThreads / 64];
+    int64_t* row = ws + (int64_t)blockIdx.x * (nchunks + 1);
+    int64_t carry = 0;
+    for (int64_t t0 = 0; t0 < nchunks; t0 += kScanThreads * kScanItems) {
+        const int64_t i0 = t0 + (int64_t)threadIdx.x * kScanItems;
+        int64_t v[kScanItems];
+#pragma unroll
+        for (int q = 0; q < kScanItems; ++q) v[q] = i0 + q < nchunks ? row[i0 + q] : 0;
+        const int64_t total = block_exclusive<kScanItems>(v, s_wave);
+#pragma unroll
+        for (int q = 0; q < kScanItems; ++q)
+            if (i0 + q < nchunks) row[i0 + q] = carry + v[q];
+        carry += total;
+    }
+    if (threadIdx.x == 0) row[nchunks] = carry;
+}
+
+// one workgroup: offsets[k] = members of the regions before k, offsets[K] = all
+__global__ __launch_bounds__(kScanThreads) void crop_offsets_kernel(const int64_t* __restrict__ ws, int64_t nchunks, int K,
+                                                                    int64_t* __restrict__ offsets) {
+    __shared__ int64_t s_wave[kScanThreads / 64];
+    int64_t carry = 0;
+    for (int k0 = 0; k0 < K; k0 += kScanThreads) {
+        const int k = k0 + threadIdx.x;
+        int64_t v[1] = {k < K ? ws[(int64_t)k * (nchunks + 1) + nchunks] : 0};
+        const int64_t total = block_exclusive<1>(v, s_wave);
+        if (k < K) offsets[k] = carry + v[0];
+        carry += total;
+    }
+    if (threadIdx.x == 0) offsets[K] = carry;
+}
+
+// (waves_per_eu 3: left alone the allocator takes 170 VGPRs, two over the limit of three waves per SIMD; at 168 it still
+// needs no scratch -- at four waves it would -- and the scatter, which waits on HBM, is 8-15 % faster on the part)
+__global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(3))) void crop_scatter_kernel(const uint64_t* __restrict__ pts,
+                                                              const uint64_t* __restrict__ labels, int64_t n,
+                                                              const double* __restrict__ regions,
+                                                              const int32_t* __restrict__ kinds, int K, int64_t nchunks,
+                                                              const int64_t* __restrict__ ws,
+                                                              const int64_t* __restrict__ offsets, int64_t capacity,
+                                                              uint64_t* __restrict__ out_pts, uint64_t* __restrict__ out_labels,
+                                                              int64_t* __restrict__ out_src) {
+    const int lane = threadIdx.x;
+    const int64_t chunk = blockIdx.x, base = chunk * kChunk;
+    uint64_t x[kGroups], y[kGroups];
+    load_xy(pts, n, base, lane, x, y);
+    for (int k0 = 0; k0 < K; k0 += kLanes) {
+        const int k = k0 + lane;
+        const Region mine = load_region(regions, kinds, K, k);
+        int64_t myfirst = 0, mycount = 0;
+        if (k < K) {
+            const int64_t* slot = ws + (int64_t)k * (nchunks + 1) + chunk;
+            const int64_t before = slot[0];
+            mycount = slot[1] - before;      // (slot[1] of the last chunk is the region's total)
+            myfirst = offsets[k] + before;
+        }
+        // regions with a member in this chunk, by the count pass's own test: the others are skipped exactly
+        unsigned long long live = __ballot(mycount != 0);
+        while (live) {
+            const int j = __ffsll(live) - 1;
+            live &= live - 1;
+            const Region R = broadcast(mine, j);
+            int64_t row = (int64_t)readlane64((uint64_t)myfirst, j);
+#pragma unroll
+            for (int g = 0; g < kGroups; ++g) {
+                const bool in = member(R, __longlong_as_double((long long)x[g]), __longlong_as_double((long long)y[g]));
+                const unsigned long long mask = __ballot(in);
+                if (in) {
+                    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+                    const int64_t o = row + rank;
+                    if ((uint64_t)o < (uint64_t)capacity) {   // (also keeps a workspace that is not this call's inside the buffer)
+                        const int64_t i = base + g * kLanes + lane;
+                        uint64_t* p = out_pts + o * 3;
+                        p[0] = x[g];
+                        p[1] = y[g];
+                        p[2] = pts[i * 3 + 2];
+                        if (out_labels) out_labels[o] = labels[i];
+                        if (out_src) out_src[o] = i;
+                    }
+                }
+                row += __popcll(mask);
+            }
+        }
+    }
+}
+
+bool shape_served(int64_t n, int K) { return n > 0 && K > 0 && n <= kMaxN && K <= kMaxK; }
+int64_t host_nchunks(int64_t n) { return (n + kChunk - 1) / kChunk; }
+
+// the checks both entries share; `what` names the entry in the error text
+int check_common(const char* what, const void* pts, int64_t n, const void* regions, const void* kinds, int K, const void* ws,
+                 size_t ws_bytes, const void* offsets) {
+    if (!pts) return sn::fail(SN_ERR_INVALID_ARG, "%s: pts is null", what);
+    if (!regions) return sn::fail(SN_ERR_INVALID_ARG, "%s: regions is null", what);
+    if (!ws) return sn::fail(SN_ERR_INVALID_ARG, "%s: ws is null", what);
+    if (!offsets) return sn::fail(SN_ERR_INVALID_ARG, "%s: offsets is null", what);
+    if (n <= 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: n must be positive (got %lld)", what, (long long)n);
+    if (K <= 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: K must be positive (got %d)", what, K);
+    if (!shape_served(n, K))
+        return sn::fail(SN_ERR_UNSUPPORTED, "%s: n=%lld, K=%d beyond what is served (n <= 2^36, K <= %d)", what, (long long)n,
+                        K, kMaxK);
+    if (ws_bytes < sn_crops_ws_bytes(n, K))
+        return sn::fail(SN_ERR_INVALID_ARG, "%s: workspace of %zu bytes, sn_crops_ws_bytes asks for %zu", what, ws_bytes,
+                        sn_crops_ws_bytes(n, K));
+    if ((uintptr_t)pts % 8 || (uintptr_t)regions % 8 || (uintptr_t)ws % 8 || (uintptr_t)offsets % 8 || (uintptr_t)kinds % 4)
+        return sn::fail(SN_ERR_INVALID_ARG, "%s: pts / regions / ws / offsets must be 8-byte, kinds 4-byte aligned", what);
+    return SN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t sn_crops_ws_bytes(int64_t n, int K) {
+    if (!shape_served(n, K)) return 0;
+    return (size_t)K * (size_t)(host_nchunks(n) + 1) * sizeof(int64_t);
+}
+
+extern "C" int sn_crops_chunk_points(void) { return kChunk; }
+
+extern "C" int sn_crop_count(const double* pts, int64_t n, const double* regions, const int32_t* kinds, int K, void* ws,
+                             size_t ws_bytes, int64_t* offsets, sn_stream_t stream) {
+    const int rc = check_common("sn_crop_count", pts, n, regions, kinds, K, ws, ws_bytes, offsets);
+    if (rc != SN_OK) return rc;
+    hipStream_t s = sn::as_stream(stream);
+    const int64_t nchunks = host_nchunks(n);
+    int64_t* w = static_cast<int64_t*>(ws);
+    hipLaunchKernelGGL(crop_count_kernel, dim3((unsigned)nchunks), dim3(kLanes), 0, s,
+                       reinterpret_cast<const uint64_t*>(pts), n, regions, kinds, K, nchunks, w);
+    hipLaunchKernelGGL(crop_prefix_kernel, dim3((unsigned)K), dim3(kScanThreads), 0, s, w, nchunks);
+    hipLaunchKernelGGL(crop_offsets_kernel, dim3(1), dim3(kScanThreads), 0, s, w, nchunks, K, offsets);
+    return sn::check_launch("sn_crop_count");
+}
+
+extern "C" int sn_crop_scatter(const double* pts, const double* labels, int64_t n, const double* regions,
+                               const int32_t* kinds, int K, const void* ws, size_t ws_bytes, const int64_t* offsets,
+                               int64_t capacity, double* out_pts, double* out_labels, int64_t* out_src, sn_stream_t stream) {
+    const int rc = check_common("sn_crop_scatter", pts, n, regions, kinds, K, ws, ws_bytes, offsets);
+    if (rc != SN_OK) return rc;
+    if (!out_pts) return sn::fail(SN_ERR_INVALID_ARG, "sn_crop_scatter: out_pts is null");
+    if (capacity < 0)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_crop_scatter: capacity must not be negative (got %lld)", (long long)capacity);
+    if ((labels == nullptr) != (out_labels == nullptr))
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_crop_scatter: out_labels is given iff labels is");
+    if ((uintptr_t)labels % 8 || (uintptr_t)out_pts % 8 || (uintptr_t)out_labels % 8 || (uintptr_t)out_src % 8)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_crop_scatter: labels / out_pts / out_labels / out_src must be 8-byte aligned");
+    const int64_t nchunks = host_nchunks(n);
+    hipLaunchKernelGGL(crop_scatter_kernel, dim3((unsigned)nchunks), dim3(kLanes), 0, sn::as_stream(stream),
+                       reinterpret_cast<const uint64_t*>(pts), reinterpret_cast<const uint64_t*>(labels), n, regions, kinds, K,
+                       nchunks, static_cast<const int64_t*>(ws), offsets, capacity, reinterpret_cast<uint64_t*>(out_pts),
+                       reinterpret_cast<uint64_t*>(out_labels), out_src);
+    return sn::check_launch("sn_crop_scatter");
+}
