@@ -17,8 +17,10 @@ FLAGS_metrics := -ffp-contract=off
 FLAGS_towers := -ffp-contract=off
 # crops.hip: the disc test's fp64 products and sum are rounded once each, as numpy rounds them
 FLAGS_crops := -ffp-contract=off
+# dbscan.hip: the neighbour test's fp64 products and sums are rounded once each, in the documented order
+FLAGS_dbscan := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

@@ -787,6 +787,92 @@ int sn_crop_scatter(const double* pts, const double* labels, int64_t n, const do
                     double* out_labels, int64_t* out_src, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K10 -- point DBSCAN: the towers of a labelled scan, on the device.
+ * replaces: select_object -> extract_towers (utils/pcd_processing.py:508-522, 577-651: np.isin over the classes, open3d's
+ *           cluster_dbscan(eps=10, min_points=300) over the tower points of a whole scan and a pandas group-by, on the
+ *           host) in front of crop_tower_samples and crop_two_towers_samples (:765-817), hence of build_data_samples
+ *           (core/datasets/ts40k.py:86-92).
+ *
+ * inputs:    pts [n,3] f64; optionally labels [n] f64 and keep [n_keep] f64: a point is selected iff label == keep[j] for
+ *            some j (np.isin: a NaN label is never selected); without labels every point is selected
+ * positions: the selected points keep scan order; their positions 0..m-1 are what "index" means below
+ * neighbour: q is a neighbour of p iff (dx*dx + dy*dy) + dz*dz <= eps*eps in fp64, in exactly this form, each product and
+ *            sum rounded once and never contracted; p is its own neighbour.  The comparison is literal: a point with a NaN
+ *            or infinite coordinate is nobody's neighbour, not even its own, and ends as noise
+ * core:      a point with at least min_points neighbours
+ * cluster:   a connected component of the cores under the neighbour relation; ids 0..K-1 ascend with each cluster's
+ *            smallest core position
+ * border:    a point that is not core and has a core neighbour: takes the smallest id among its core neighbours
+ * noise:     everything else, labelled -1
+ * (sklearn.cluster.DBSCAN(algorithm='kd_tree') gives these labels, borders included, on sets without a pair on the rim;
+ * open3d's boundary rule and its choice for a border two clusters reach could not be checked and are unpinned, as for K8.)
+ * ------------------------------------------------------------------------- */
+#define SN_DBSCAN_NSTAT 3      /* n_points, n_core, first core's scan index */
+#define SN_DBSCAN_LAUNCHES 8   /* cells, prefix, scatter, core, union, flatten, rank, finish */
+
+/* Scan points per workgroup of sn_points_select (1024) and positions per workgroup of sn_dbscan_points (256): host only
+ * -- they let a test put its sizes on the seams. */
+int sn_points_select_chunk_points(void);
+int sn_dbscan_chunk_points(void);
+
+/* Workspace bytes of sn_points_select over n points (56 per 1024 points); 0 for n <= 0 or n > 2^33. */
+size_t sn_points_select_ws_bytes(int64_t n);
+
+/* sel [capacity] i64 (null iff capacity == 0): the scan indices of the selected points, ascending -- scan order by
+ * construction (ballot and mbcnt ranks, as K9).  n_sel [1] i64: the TRUE count whatever the capacity; rows at or beyond
+ * capacity are not touched.  bbox [6] f64 = (xmin, ymin, zmin, xmax, ymax, zmax) over the selected points' finite
+ * coordinates, each axis by itself (+inf, -inf where there is none).  labels null: every point is selected, keep is not
+ * read.  keep lives on the DEVICE.  Three launches (count, prefix, scatter), every slot written by one workgroup: no
+ * atomics, no allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null pts / ws / n_sel / bbox, labels without keep, n <= 0, n_keep < 0, capacity < 0, sel null with
+ * capacity > 0, a short workspace, a pointer not 8-byte aligned;  SN_ERR_UNSUPPORTED: n > 2^33, n_keep > 64. */
+int sn_points_select(const double* pts, const double* labels, int64_t n, const double* keep, int n_keep, int64_t capacity,
+                     void* ws, size_t ws_bytes, int64_t* sel, int64_t* n_sel, double* bbox, sn_stream_t stream);
+
+/* The search grid of sn_dbscan_points: cubic cells of side k * eps (times 1 + 2^-20, so that rounding of a cell index can
+ * never put two neighbours two cells apart) over bounds_host = (xmin, ymin, zmin, xmax, ymax, zmax), dims = floor(extent /
+ * side) + 1 per axis, with the smallest integer k >= 1 whose grid has at most max_cells cells.  dims_out [3] i32 and
+ * side_out [1] (both nullable).  Host only, no GPU.
+ * SN_ERR_INVALID_ARG: null bounds, eps <= 0 or not finite, max_cells < 1, a bound that is not finite, max < min;
+ * SN_ERR_UNSUPPORTED: eps outside 1e-150 .. 1e150, max_cells > 2^22. */
+int sn_dbscan_cell_grid(const double* bounds_host, double eps, int64_t max_cells, int32_t* dims_out, double* side_out);
+
+/* Workspace bytes of sn_dbscan_points for `capacity` positions and `cells` grid cells (48 B per position, 8 B per cell);
+ * 0 for what the entry refuses (capacity < 1 or >= 2^31, cells < 1 or > 2^22). */
+size_t sn_dbscan_ws_bytes(int64_t capacity, int64_t cells);
+
+/* Clusters the first min(n_sel, capacity) selected positions of pts [n,3].  sel [>= capacity] i64: their scan indices
+ * (null: the identity over the scan's n rows; an index outside 0..n-1 reads as a NaN point); n_sel [1] i64 on the DEVICE
+ * (null allowed with a null sel: n).  bounds_host, eps, max_cells: the grid of sn_dbscan_cell_grid, read during the call
+ * only (it travels as a kernel argument: a captured replay keeps that of capture time).  A point outside the bounds or
+ * with a non-finite coordinate is clamped into an edge cell; clamping never moves two cells apart that were adjacent, so
+ * the result is exact for ANY bounds -- they only decide the speed.
+ * cluster [capacity] i32: one label per position, rows at or beyond min(n_sel, capacity) not touched.  n_clusters [1] i32:
+ * the true K, never clipped.  stats [max_clusters, SN_DBSCAN_NSTAT] i64 (null iff max_clusters == 0): rows of the ids
+ * below max_clusters, zero rows for absent ones.  status [1] i32, WRITTEN by the call: bit 0 iff n_sel > capacity.
+ * ws: caller-owned scratch of ws_bytes >= sn_dbscan_ws_bytes(capacity, cells of the grid), 16-byte aligned.
+ * A memset node and SN_DBSCAN_LAUNCHES launches on `stream`; lock-free union-find over positions (compare-and-swap on
+ * parents that only decrease), every loop bounded by the data, no workgroup waits for another; integer atomics only:
+ * results do not depend on scheduling.  No allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null pts / ws / cluster / n_clusters / status / bounds, sel without n_sel, n <= 0, capacity <= 0,
+ * min_points < 1, eps <= 0 or not finite, max_clusters < 0, stats null with max_clusters > 0, what sn_dbscan_cell_grid
+ * calls invalid, a short workspace, a misaligned pointer;  SN_ERR_UNSUPPORTED: capacity >= 2^31, n > 2^33, max_clusters >
+ * 2^20, what sn_dbscan_cell_grid calls unsupported. */
+int sn_dbscan_points(const double* pts, int64_t n, const int64_t* sel, const int64_t* n_sel, int64_t capacity,
+                     const double* bounds_host, double eps, int min_points, int64_t max_cells, int max_clusters, void* ws,
+                     size_t ws_bytes, int32_t* cluster, int32_t* n_clusters, int64_t* stats, int32_t* status,
+                     sn_stream_t stream);
+
+/* DIAGNOSTIC entry, no part of the stable interface: the launches first..last (1-based, of SN_DBSCAN_LAUNCHES) of the same
+ * call and nothing else; tools/dbscan_bench.py times the prefixes 1..k through it and takes differences.  Launches left
+ * out must have run before on the same workspace. */
+int sn_dbscan_points_launches(const double* pts, int64_t n, const int64_t* sel, const int64_t* n_sel, int64_t capacity,
+                              const double* bounds_host, double eps, int min_points, int64_t max_cells, int max_clusters,
+                              void* ws, size_t ws_bytes, int32_t* cluster, int32_t* n_clusters, int64_t* stats,
+                              int32_t* status, int first, int last, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,16 @@ SYMBOLS = {
     "sn_crop_count": (c_int, [_P, ctypes.c_int64, _P, _P, _I, _P, ctypes.c_size_t, _P, _P]),
     "sn_crop_scatter": (c_int, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P, _P,
                                 _P]),
+    "sn_points_select_chunk_points": (c_int, []),
+    "sn_dbscan_chunk_points": (c_int, []),
+    "sn_points_select_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "sn_points_select": (c_int, [_P, _P, ctypes.c_int64, _P, _I, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P, _P, _P]),
+    "sn_dbscan_cell_grid": (c_int, [_P, ctypes.c_double, ctypes.c_int64, _P, _P]),
+    "sn_dbscan_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "sn_dbscan_points": (c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, ctypes.c_double, _I, ctypes.c_int64, _I, _P,
+                                 ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "sn_dbscan_points_launches": (c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, ctypes.c_double, _I, ctypes.c_int64,
+                                          _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _I, _I, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -118,6 +128,7 @@ SN_METRIC_WS_BYTES = SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8
 SN_CURVE_MAX_THRESHOLDS = 255
 SN_TOWER_NSTAT, SN_TOWER_LAUNCHES, SN_TOWER_MAX_RADIUS = 12, 6, 10
 SN_CROP_DISC, SN_CROP_BOX = 0, 1
+SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1322,3 +1333,108 @@ def crop_scatter(pts: torch.Tensor, labels: Optional[torch.Tensor], regions: tor
                                 _ptr(out_labels, torch.float64, "out_labels"), _ptr(out_src, torch.int64, "out_src"),
                                 _stream())
     _check(rc, "sn_crop_scatter")
+
+
+# --------------------------------------------------------------------------- #
+def points_select_chunk_points() -> int:
+    """sn_points_select_chunk_points: scan points per workgroup of the select kernels (host only)."""
+    return int(load().sn_points_select_chunk_points())
+
+
+def dbscan_chunk_points() -> int:
+    """sn_dbscan_chunk_points: positions per workgroup of the clustering kernels (host only)."""
+    return int(load().sn_dbscan_chunk_points())
+
+
+def points_select_ws_bytes(n: int) -> int:
+    """sn_points_select_ws_bytes: scratch bytes of points_select over n points (host only)."""
+    need = int(load().sn_points_select_ws_bytes(int(n)))
+    if need == 0:
+        raise HipLibraryError(f"sn_points_select serves no scan of {n} points (1 <= n <= 2^33)")
+    return need
+
+
+def _bounds_c(bounds):
+    if isinstance(bounds, ctypes.Array):
+        return bounds
+    vals = [float(v) for v in bounds]
+    if len(vals) != 6:
+        raise ValueError("bounds must have 6 entries: xmin, ymin, zmin, xmax, ymax, zmax")
+    return (ctypes.c_double * 6)(*vals)
+
+
+def dbscan_cell_grid(bounds, eps: float, max_cells: int) -> Tuple[Tuple[int, int, int], float]:
+    """sn_dbscan_cell_grid (host only): ((dims per axis), cell side) of the search grid over bounds = (xmin, ymin, zmin,
+    xmax, ymax, zmax)."""
+    dims = (ctypes.c_int32 * 3)()
+    side = ctypes.c_double(0.0)
+    b = _bounds_c(bounds)
+    _check(load().sn_dbscan_cell_grid(ctypes.cast(b, c_void_p), float(eps), int(max_cells), ctypes.cast(dims, c_void_p),
+                                      ctypes.cast(ctypes.pointer(side), c_void_p)), "sn_dbscan_cell_grid")
+    return (int(dims[0]), int(dims[1]), int(dims[2])), float(side.value)
+
+
+def dbscan_ws_bytes(capacity: int, cells: int) -> int:
+    """sn_dbscan_ws_bytes: scratch bytes of dbscan_points for `capacity` positions and `cells` grid cells (host only)."""
+    need = int(load().sn_dbscan_ws_bytes(int(capacity), int(cells)))
+    if need == 0:
+        raise HipLibraryError(f"sn_dbscan_points serves no {capacity} positions on {cells} cells (1 <= capacity < 2^31, "
+                              "1 <= cells <= 2^22)")
+    return need
+
+
+@_on_tensor_device
+def points_select(pts: torch.Tensor, labels: Optional[torch.Tensor], keep: Optional[torch.Tensor], ws: torch.Tensor,
+                  sel: Optional[torch.Tensor], n_sel: torch.Tensor, bbox: torch.Tensor,
+                  capacity: Optional[int] = None) -> None:
+    """sn_points_select: pts [n,3] f64, labels [n] f64 | None, keep [n_keep] f64 (device) -> sel [capacity] i64, n_sel [1]
+    i64 (the true count), bbox [6] f64, all caller-owned like the scratch `ws` (points_select_ws_bytes).  Three launches,
+    no allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [n, 3] (got {tuple(pts.shape)})")
+    n = int(pts.shape[0])
+    if labels is not None and labels.numel() != n:
+        raise HipLibraryError("labels and pts disagree in length")
+    rows = 0 if sel is None else int(sel.numel())
+    capacity = rows if capacity is None else int(capacity)
+    if capacity > rows:
+        raise HipLibraryError("capacity exceeds the rows of sel")
+    if n_sel.numel() != 1 or bbox.numel() != 6:
+        raise HipLibraryError("n_sel must hold 1 entry and bbox 6")
+    rc = load().sn_points_select(_ptr(pts, torch.float64, "pts"), _ptr(labels, torch.float64, "labels"), n,
+                                 _ptr(keep, torch.float64, "keep"), 0 if keep is None else int(keep.numel()), capacity,
+                                 _ptr(ws, None, "ws"), ws.numel() * ws.element_size(),
+                                 _ptr(sel, torch.int64, "sel") if capacity > 0 else None, _ptr(n_sel, torch.int64, "n_sel"),
+                                 _ptr(bbox, torch.float64, "bbox"), _stream())
+    _check(rc, "sn_points_select")
+
+
+@_on_tensor_device
+def dbscan_points(pts: torch.Tensor, sel: Optional[torch.Tensor], n_sel: Optional[torch.Tensor], bounds, eps: float,
+                  min_points: int, max_cells: int, max_clusters: int, ws: torch.Tensor, cluster: torch.Tensor,
+                  n_clusters: torch.Tensor, stats: Optional[torch.Tensor], status: torch.Tensor,
+                  capacity: Optional[int] = None, launches: Optional[Tuple[int, int]] = None) -> None:
+    """sn_dbscan_points over the positions sel [>= capacity] i64 (None: the scan's own rows) of pts [n,3] f64: cluster
+    [capacity] i32, n_clusters [1] i32, stats [max_clusters, SN_DBSCAN_NSTAT] i64, status [1] i32, all caller-owned like
+    the scratch `ws` (dbscan_ws_bytes).  bounds: 6 floats or a ctypes array built once.  launches = (first, last): only
+    those of the SN_DBSCAN_LAUNCHES launches (sn_dbscan_points_launches: timing).  No allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [n, 3] (got {tuple(pts.shape)})")
+    n = int(pts.shape[0])
+    capacity = int(cluster.numel()) if capacity is None else int(capacity)
+    max_clusters = int(max_clusters)
+    if capacity > cluster.numel() or (sel is not None and sel.numel() < capacity):
+        raise HipLibraryError("capacity exceeds the rows of cluster / sel")
+    if n_clusters.numel() != 1 or status.numel() != 1 or (n_sel is not None and n_sel.numel() != 1) or \
+            (stats is not None and stats.numel() != max_clusters * SN_DBSCAN_NSTAT):
+        raise HipLibraryError("n_clusters / status / n_sel / stats do not have the sizes of this call")
+    b = _bounds_c(bounds)
+    head = (_ptr(pts, torch.float64, "pts"), n, _ptr(sel, torch.int64, "sel"), _ptr(n_sel, torch.int64, "n_sel"), capacity,
+            ctypes.cast(b, c_void_p), float(eps), int(min_points), int(max_cells), max_clusters, _ptr(ws, None, "ws"),
+            ws.numel() * ws.element_size(), _ptr(cluster, torch.int32, "cluster"), _ptr(n_clusters, torch.int32, "n_clusters"),
+            _ptr(stats, torch.int64, "stats"), _ptr(status, torch.int32, "status"))
+    if launches is None:
+        rc = load().sn_dbscan_points(*head, _stream())
+    else:
+        rc = load().sn_dbscan_points_launches(*head, int(launches[0]), int(launches[1]), _stream())
+    _check(rc, "sn_dbscan_points")

@@ -191,11 +191,16 @@ def crop_two_towers(xyz: torch.Tensor, classes: torch.Tensor, xyz_tower1: torch.
     return crops.pts, crops.labels.to(torch.int64)
 
 
-def crop_tower_samples(xyz: torch.Tensor, classes: torch.Tensor, towers: Sequence[torch.Tensor], radius: float = 15
-                       ) -> List[torch.Tensor]:
-    """pcd_processing.py:805-817 with the towers GIVEN as a list of point sets (the reference finds them with a point-level
-    DBSCAN in front, which is not mirrored): one [n_k, 4] sample (x, y, z, class) per tower, all cut in one pass.  Tower
-    means as in crop_tower_radius."""
+def crop_tower_samples(xyz: torch.Tensor, classes: torch.Tensor, towers: Optional[Sequence[torch.Tensor]] = None,
+                       radius: float = 15, obj_class=(15,), eps: float = 10, min_points: int = 300) -> List[torch.Tensor]:
+    """pcd_processing.py:805-817: one [n_k, 4] sample (x, y, z, class) per tower, all cut in one pass.  towers None (the
+    reference's own signature): the towers are found on the device as the reference finds them -- the points whose class
+    is one of obj_class, clustered by DBSCAN(eps, min_points) (clusters.cluster_points).  towers given as a list of point
+    sets: those are taken, and obj_class / eps / min_points are not read.  Tower means as in crop_tower_radius."""
+    if towers is None:
+        from .clusters import cluster_points
+        xyz = _device_f64(xyz, "xyz")
+        towers = cluster_points(xyz, eps, min_points, labels=_device_f64(classes, "classes"), keep=obj_class).towers()
     if len(towers) == 0:
         return []
     xyz = _device_f64(xyz, "xyz")
