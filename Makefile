@@ -19,8 +19,10 @@ FLAGS_towers := -ffp-contract=off
 FLAGS_crops := -ffp-contract=off
 # dbscan.hip: the neighbour test's fp64 products and sums are rounded once each, in the documented order
 FLAGS_dbscan := -ffp-contract=off
+# tower_score.hip: centroids, means and distances are fp64 operations rounded once each, in numpy's order
+FLAGS_tower_score := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

@@ -873,6 +873,91 @@ int sn_dbscan_points_launches(const double* pts, int64_t n, const int64_t* sel, 
                               int32_t* status, int first, int last, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K11 -- tower scores: K8's statistics rows filtered, merged and matched against the ground truth's towers, on the device.
+ * All arithmetic is fp64, each operation rounded once, in exactly the written order (built with -ffp-contract=off; sqrt is
+ * the correctly rounded one).
+ *
+ * Inputs per tile b: stats[b, 0..K-1, SN_TOWER_NSTAT] and n_towers[b] of sn_tower_proposals.  Row i is PRESENT if
+ * i < min(n_towers[b], K) and n_voxels > 0.  s = voxel size per grid axis (null: 1, 1, 1; each finite and > 0),
+ * h = height_axis in {0, 1, 2}, (p0, p1) the other two axes, ascending.
+ *   centroid    c_a = ((double)sum_a / (double)n_voxels) * s_a
+ *   extent      e_a = (double)max_a * s_a - (double)min_a * s_a
+ *   planar row  q_i = (c_p0, c_p1)
+ * (with s = 1 these are TowerProposals.towers(b)'s centroids and box differences bit for bit)
+ *
+ * Filter (apply_filter != 0; sna.filter_towers):
+ *   keep_i = ((e_h >= tower_height) || (max(e_p0, e_p1) <= threshold))
+ *            && ((c_p0 - ctr_p0)*(c_p0 - ctr_p0) + (c_p1 - ctr_p1)*(c_p1 - ctr_p1) <= rim_sq)
+ *   rim_sq is passed as a number: the caller evaluates (radius - threshold * 2) ** 2 the way the host mirror does (Python's
+ *   ** is libm's pow, not always x*x, so the square is never recomputed here).  ctr: three host doubles in scaled units.
+ *   apply_filter == 0: every present row is kept (compute_euc_dists' form).
+ *
+ * Aggregate (sna.aggregate_centroids): over the kept rows in id order, for each i the members are the kept j with
+ *   sqrt(dx*dx + dy*dy) <= min_euc, dx = q_j0 - q_i0, dy = q_j1 - q_i1 (the sum in that order); mean_i is the members' rows
+ *   added one after another in ascending j starting from 0.0, per column, then divided by (double)count -- numpy's order for
+ *   np.mean(axis=0).  agg[b] holds the distinct mean_i rows (numeric equality on both columns) sorted ascending by column 0,
+ *   then column 1 (np.unique(axis=0)); n_agg[b] rows are valid, the rest NaN.  The relation is deliberately not transitive:
+ *   a chain A-B-C with A, C further apart than min_euc has three different means and gives three rows.
+ *
+ * Match (compute_euc_dists; neither a filter nor an aggregation on the ground-truth side): for each present ground-truth
+ *   row k with planar row g_k (same coordinate rule on gt_stats):
+ *   d_m = sqrt((g_k0 - a_m0)*(g_k0 - a_m0) + (g_k1 - a_m1)*(g_k1 - a_m1)) over m < n_agg; match[b,k] is the first m of the
+ *   smallest d_m, dist[b,k] that d_m.  n_agg == 0: match = -1, dist = 0.0 (the reference's (gt_c, None, 0)).  Absent rows:
+ *   match = -1, dist = NaN.
+ *
+ * Status: status[b] bit 0 is set when n_towers[b] > K: rows are missing, the outputs cover the rows that exist.
+ *
+ * Totals: int64[SN_TSCORE_NTOTAL], accumulated into, never zeroed by the call:
+ *   tiles, tiles_skipped, gt_towers, proposals (sum of n_agg), hits (match >= 0 && dist <= hit_dist),
+ *   misses (gt_towers - hits), false_proposals (aggregated rows that are the match of no hit), one reserved 0.
+ *   A tile with bit 0 set on either side adds 1 to tiles_skipped and nothing else.
+ * dist_total: one fp64; the sum of the hits' dist is added to it, deterministically (identical bits for identical inputs
+ *   and prior contents): no fp atomics, a per-tile partial in row order and a fixed-shape reduction over the tiles in a
+ *   second small launch.  It may differ from the tile-order sum by at most hits * 2^-53 * sum(dist), the bound of any
+ *   summation order.
+ *
+ * Not mirrored: get_tower_proposals' "remove buggy centroid" step (utils/observer_utils.py:567-572) drops one cluster whose
+ * centroid is exactly (0, 0, 0).  That can only be the single voxel (0, 0, 0), which no min_points >= 2 produces.
+ * ------------------------------------------------------------------------- */
+#define SN_TSCORE_MAX_ROWS 1024   /* rows per tile either entry serves (the tile's planar rows live in LDS) */
+#define SN_TSCORE_NTOTAL 8        /* tiles, tiles_skipped, gt_towers, proposals, hits, misses, false_proposals, reserved */
+
+/* replaces: filter_towers (utils/observer_utils.py:503-549) and aggregate_centroids (:476-500) as get_tower_proposals
+ *           (:556-582) chains them behind extract_towers, and the aggregation loop inside compute_euc_dists (:441-454);
+ *           here on K8's statistics rows, without the per-tile copy of the label grid that TowerProposals.towers(b) needs.
+ * stats [B, max_towers, SN_TOWER_NSTAT] i64, n_towers [B] i32 (device).  voxel_size_host (nullable), center_host (needed
+ * with apply_filter): 3 doubles in HOST memory, read during the call only (they travel as kernel arguments: a captured
+ * replay keeps capture-time values).
+ * keep [B, K] u8: 1 for kept rows.  planar [B, K, 2] f64 (nullable): q of the present rows, NaN absent.  agg [B, K, 2] f64,
+ * n_agg [B] i32, status [B] i32 as defined above.
+ * One launch, one workgroup per tile, no atomics; no allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null required pointer, B <= 0, max_towers < 1, height_axis outside 0..2, a voxel size or min_euc
+ * that is not finite and positive, center_host null with apply_filter, a misaligned pointer;  SN_ERR_UNSUPPORTED: max_towers
+ * > SN_TSCORE_MAX_ROWS, B > 65535.  All checked before the launch. */
+int sn_tower_centroids(const int64_t* stats, const int32_t* n_towers, int B, int max_towers, int height_axis,
+                       const double* voxel_size_host, const double* center_host, int apply_filter, double threshold,
+                       double tower_height, double rim_sq, double min_euc, uint8_t* keep, double* planar, double* agg,
+                       int32_t* n_agg, int32_t* status, sn_stream_t stream);
+
+/* replaces: the matching loop of compute_euc_dists (utils/observer_utils.py:413-473, the loop at :456-463): for every
+ *           ground-truth tower the nearest proposed tower and their planar distance, plus running totals over tiles.
+ * agg [B, max_rows_pred, 2] f64, n_agg [B] i32, status_pred [B] i32: what sn_tower_centroids left for the prediction.
+ * gt_stats [B, max_towers_gt, SN_TOWER_NSTAT] i64, gt_n_towers [B] i32: sn_tower_proposals' rows of the ground truth.
+ * match [B, Kg] i32, dist [B, Kg] f64, gt_planar [B, Kg, 2] f64 (nullable; NaN absent) as defined above.
+ * totals i64[SN_TSCORE_NTOTAL] and dist_total f64[1]: both or neither.  hit_dist > 0, +inf allowed.
+ * One launch (one workgroup per tile, integer atomics on totals only) and, with totals, a second single-workgroup launch
+ * that sums the hits' distances per tile in row order and over the tiles in a fixed shape.  No workgroup waits for another;
+ * no allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null required pointer, B <= 0, max_rows_pred or max_towers_gt < 1, height_axis outside 0..2, a
+ * voxel size that is not finite and positive, hit_dist not positive (NaN included), a misaligned pointer, only one of totals
+ * / dist_total;  SN_ERR_UNSUPPORTED: max_rows_pred or max_towers_gt > SN_TSCORE_MAX_ROWS, B > 65535. */
+int sn_tower_match(const double* agg, const int32_t* n_agg, const int32_t* status_pred, int max_rows_pred,
+                   const int64_t* gt_stats, const int32_t* gt_n_towers, int max_towers_gt, int B, int height_axis,
+                   const double* voxel_size_host, double hit_dist, int32_t* match, double* dist, double* gt_planar,
+                   int64_t* totals, double* dist_total, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

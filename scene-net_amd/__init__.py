@@ -18,6 +18,8 @@ from .stream import TileRing, TileStream, scan_tiles
 from .training import CapturedTrainingStep, allreduce_flat_grads
 from .metrics import BinarySegmentationCurve, BinarySegmentationMetrics, init_metrics
 from .towers import TowerProposals, aggregate_centroids, filter_towers, tower_proposals
+from .tower_score import (TowerCentroids, TowerDetectionMetrics, TowerMatches, compute_euc_dists, get_tower_proposals,
+                          tower_centroids, tower_detection_values)
 from .crops import (ScanCrops, crop_at_locations, crop_regions, crop_tower_radius, crop_tower_samples, crop_two_towers,
                     lattice_regions, merge_to_scan)
 from .clusters import PointClusters, cluster_points, crop_two_towers_samples, extract_towers, select_object
@@ -28,7 +30,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "neg_sphere_kernel", "GENEO_Layer", "GENEO_kernel_torch", "cylinderv2", "arrow", "negSpherev2", "Voxelization",
            "ToTensor", "ToFullDense", "hist_on_voxel", "reg_on_voxel", "prob_to_label", "vxg_to_xyz", "voxelize_batch",
            "PointBatch", "VoxelGrids", "ScenePipeline", "CapturedPipeline", "CapturedTrainingStep", "allreduce_flat_grads", "shard_range", "TS40KTiles", "batch_to_device", "pack_csr",
-           "point_predictions", "split_tile", "TileStream", "TileRing", "scan_tiles", "BinarySegmentationMetrics", "BinarySegmentationCurve", "init_metrics", "TowerProposals", "tower_proposals", "filter_towers", "aggregate_centroids", "ScanCrops", "crop_regions", "crop_at_locations",
+           "point_predictions", "split_tile", "TileStream", "TileRing", "scan_tiles", "BinarySegmentationMetrics", "BinarySegmentationCurve", "init_metrics", "TowerProposals", "tower_proposals", "filter_towers", "aggregate_centroids", "TowerCentroids", "TowerMatches", "TowerDetectionMetrics",
+           "tower_centroids", "get_tower_proposals", "compute_euc_dists", "tower_detection_values", "ScanCrops", "crop_regions", "crop_at_locations",
            "crop_tower_radius", "crop_two_towers", "crop_tower_samples", "lattice_regions", "merge_to_scan", "PointClusters", "cluster_points", "select_object", "extract_towers",
            "crop_two_towers_samples", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",

@@ -117,6 +117,9 @@ SYMBOLS = {
                                  ctypes.c_size_t, _P, _P, _P, _P, _P]),
     "sn_dbscan_points_launches": (c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, ctypes.c_double, _I, ctypes.c_int64,
                                           _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _I, _I, _P]),
+    "sn_tower_centroids": (c_int, [_P, _P, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    "sn_tower_match": (c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -127,6 +130,7 @@ SN_METRIC_NCOUNT, SN_METRIC_NVALUE, SN_METRIC_MAX_PARTS = 6, 5, 1024
 SN_METRIC_WS_BYTES = SN_METRIC_MAX_PARTS * SN_METRIC_NCOUNT * 8
 SN_CURVE_MAX_THRESHOLDS = 255
 SN_TOWER_NSTAT, SN_TOWER_LAUNCHES, SN_TOWER_MAX_RADIUS = 12, 6, 10
+SN_TSCORE_MAX_ROWS, SN_TSCORE_NTOTAL = 1024, 8
 SN_CROP_DISC, SN_CROP_BOX = 0, 1
 SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
 OCC_MAX_WORDS = 16 * 1024
@@ -1267,6 +1271,68 @@ def tower_proposals(grid: torch.Tensor, tau: float, eps: float, min_points: int,
     else:
         rc = load().sn_tower_proposals_launches(*head, int(launches[0]), int(launches[1]), _stream())
     _check(rc, "sn_tower_proposals")
+
+
+def _double3_c(v, name):
+    if v is None or isinstance(v, ctypes.Array):
+        return v
+    vals = [float(x) for x in v]
+    if len(vals) != 3:
+        raise ValueError(f"{name} must have 3 entries, one per grid axis")
+    return (ctypes.c_double * 3)(*vals)
+
+
+@_on_tensor_device
+def tower_centroids(stats: torch.Tensor, n_towers: torch.Tensor, height_axis: int, center, apply_filter: bool,
+                    threshold: float, tower_height: float, rim_sq: float, min_euc: float, keep: torch.Tensor,
+                    planar: Optional[torch.Tensor], agg: torch.Tensor, n_agg: torch.Tensor, status: torch.Tensor,
+                    voxel_size=None) -> None:
+    """sn_tower_centroids over stats [B, K, SN_TOWER_NSTAT] i64 and n_towers [B] i32: keep [B, K] u8, planar [B, K, 2] f64
+    (or None), agg [B, K, 2] f64, n_agg [B] i32, status [B] i32, all caller-owned.  center / voxel_size: 3 floats or a
+    ctypes array built once (center may be None without the filter).  No allocation, no synchronisation."""
+    if stats.dim() != 3 or stats.shape[2] != SN_TOWER_NSTAT:
+        raise HipLibraryError(f"stats must be [B, K, {SN_TOWER_NSTAT}] (got {tuple(stats.shape)})")
+    B, K = int(stats.shape[0]), int(stats.shape[1])
+    if n_towers.numel() != B or keep.numel() != B * K or agg.numel() != 2 * B * K or n_agg.numel() != B or \
+            status.numel() != B or (planar is not None and planar.numel() != 2 * B * K):
+        raise HipLibraryError("n_towers / keep / planar / agg / n_agg / status do not have the sizes of these stats")
+    vs, ctr = _double3_c(voxel_size, "voxel_size"), _double3_c(center, "center")
+    rc = load().sn_tower_centroids(
+        _ptr(stats, torch.int64, "stats"), _ptr(n_towers, torch.int32, "n_towers"), B, K, int(height_axis),
+        ctypes.cast(vs, c_void_p) if vs is not None else None, ctypes.cast(ctr, c_void_p) if ctr is not None else None,
+        1 if apply_filter else 0, float(threshold), float(tower_height), float(rim_sq), float(min_euc),
+        _ptr(keep, torch.uint8, "keep"), _ptr(planar, torch.float64, "planar"), _ptr(agg, torch.float64, "agg"),
+        _ptr(n_agg, torch.int32, "n_agg"), _ptr(status, torch.int32, "status"), _stream())
+    _check(rc, "sn_tower_centroids")
+
+
+@_on_tensor_device
+def tower_match(agg: torch.Tensor, n_agg: torch.Tensor, status_pred: torch.Tensor, gt_stats: torch.Tensor,
+                gt_n_towers: torch.Tensor, height_axis: int, hit_dist: float, match: torch.Tensor, dist: torch.Tensor,
+                gt_planar: Optional[torch.Tensor] = None, totals: Optional[torch.Tensor] = None,
+                dist_total: Optional[torch.Tensor] = None, voxel_size=None) -> None:
+    """sn_tower_match: agg [B, Kp, 2] f64, n_agg / status_pred [B] i32 of tower_centroids against gt_stats [B, Kg,
+    SN_TOWER_NSTAT] i64, gt_n_towers [B] i32 -> match [B, Kg] i32, dist [B, Kg] f64, gt_planar [B, Kg, 2] f64 (or None);
+    totals i64[SN_TSCORE_NTOTAL] and dist_total f64[1] (both or neither) are accumulated into.  No allocation, no
+    synchronisation."""
+    if agg.dim() != 3 or agg.shape[2] != 2:
+        raise HipLibraryError(f"agg must be [B, K, 2] (got {tuple(agg.shape)})")
+    if gt_stats.dim() != 3 or gt_stats.shape[2] != SN_TOWER_NSTAT or gt_stats.shape[0] != agg.shape[0]:
+        raise HipLibraryError(f"gt_stats must be [{agg.shape[0]}, Kg, {SN_TOWER_NSTAT}] (got {tuple(gt_stats.shape)})")
+    B, Kp, Kg = int(agg.shape[0]), int(agg.shape[1]), int(gt_stats.shape[1])
+    if n_agg.numel() != B or status_pred.numel() != B or gt_n_towers.numel() != B or match.numel() != B * Kg or \
+            dist.numel() != B * Kg or (gt_planar is not None and gt_planar.numel() != 2 * B * Kg) or \
+            (totals is not None and totals.numel() != SN_TSCORE_NTOTAL) or (dist_total is not None and dist_total.numel() != 1):
+        raise HipLibraryError("n_agg / status_pred / gt_n_towers / match / dist / gt_planar / totals / dist_total do not have "
+                              "the sizes of agg and gt_stats")
+    vs = _double3_c(voxel_size, "voxel_size")
+    rc = load().sn_tower_match(
+        _ptr(agg, torch.float64, "agg"), _ptr(n_agg, torch.int32, "n_agg"), _ptr(status_pred, torch.int32, "status_pred"),
+        Kp, _ptr(gt_stats, torch.int64, "gt_stats"), _ptr(gt_n_towers, torch.int32, "gt_n_towers"), Kg, B, int(height_axis),
+        ctypes.cast(vs, c_void_p) if vs is not None else None, float(hit_dist), _ptr(match, torch.int32, "match"),
+        _ptr(dist, torch.float64, "dist"), _ptr(gt_planar, torch.float64, "gt_planar"), _ptr(totals, torch.int64, "totals"),
+        _ptr(dist_total, torch.float64, "dist_total"), _stream())
+    _check(rc, "sn_tower_match")
 
 
 # --------------------------------------------------------------------------- #
