@@ -788,6 +788,47 @@ int sn_crop_scatter(const double* pts, const double* labels, int64_t n, const do
 
 
 /* ------------------------------------------------------------------------- *
+ * K12 -- region census: what the labels inside each of K9's regions are, before anything is cut.
+ * replaces: the per-candidate crop, read-back and numpy pass by which the reference decides whether a region becomes a
+ *           sample -- crop_ground_samples (utils/pcd_processing.py:742-762: more than 300 points, at least two classes,
+ *           no tower), build_pole_samples (core/datasets/semKITTI.py:37-88: at least 5 pole points per slab),
+ *           build_pole_radius_samples (:105-158: at least 5 per disc) and the scan-level gates np.any(classes == TOWER)
+ *           (ts40k.py:88) / np.any(gt == pole_label) (semKITTI.py:142).
+ *
+ * scan, regions, kinds: as K9, and MEMBERSHIP IS K9's, bit for bit (the same device function): the disc and box tests of
+ *           the K9 block, kinds null = all discs, any other kind an empty region, a NaN x or y in no region.
+ * watch:    [C,2] f64 on the device, C <= SN_CENSUS_MAX_WATCH inclusive ranges (lo, hi) of label values
+ * output:   counts [K, 2 + C] i64:  [k][0] members;  [k][1] members whose label is NaN (0 without labels);
+ *           [k][2 + c] members with watch[c][0] <= label && label <= watch[c][1], taken literally: a NaN label or a NaN
+ *           bound never matches.  Equality with v is (v, v); trunc(label) == v for v > 0 is (v, nextafter(v + 1, -inf)).
+ *           label_range [K,2] f64: (min, max) over the members' labels that are not NaN, in the order that puts -0.0 below
+ *           +0.0 -- a definite bit pattern; (+inf, -inf) for a region with no such member.
+ *           "At least two distinct label values" as np.unique counts them (all NaNs one value) is
+ *           min < max || (n_nan > 0 && n_nan < n).
+ *           Every output is an integer sum or a maximum of integer codes: it does not depend on scheduling.
+ * ------------------------------------------------------------------------- */
+#define SN_CENSUS_MAX_WATCH 16
+
+/* Workspace bytes of sn_crop_census: 8 * 8 * K * (C + 4) -- eight shards of K rows of C + 4 words.  0 for a shape the entry refuses (n <= 0, K <= 0, n > 2^36,
+ * K > 65536, C < 0, C > SN_CENSUS_MAX_WATCH). */
+size_t sn_crop_census_ws_bytes(int64_t n, int K, int C);
+/* Points per workgroup of the census kernel (1024): host only -- lets a test put its sizes on the seams. */
+int sn_census_chunk_points(void);
+
+/* One memset node over ws and two launches on `stream`: the census (one wave per sn_census_chunk_points() points; what a
+ * workgroup finds is reduced over the wave and added to the region's row in one of ws' eight shards by 64-bit integer atomic add / max, only
+ * where it is not zero) and a decode that folds the shards into counts and label_range.  No floating-point atomics, no workgroup waits
+ * for another, no allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null pts / regions / ws / counts, n <= 0, K <= 0, C < 0, C > 0 without labels, watch given with
+ * C == 0 or missing with C > 0, label_range given without labels or missing with them, ws_bytes <
+ * sn_crop_census_ws_bytes(n, K, C), a misaligned pointer (8 bytes; kinds 4);
+ * SN_ERR_UNSUPPORTED: n > 2^36, K > 65536 or C > SN_CENSUS_MAX_WATCH. */
+int sn_crop_census(const double* pts, const double* labels, int64_t n, const double* regions, const int32_t* kinds, int K,
+                   const double* watch, int C, void* ws, size_t ws_bytes, int64_t* counts, double* label_range,
+                   sn_stream_t stream);
+
+
+/* ------------------------------------------------------------------------- *
  * K10 -- point DBSCAN: the towers of a labelled scan, on the device.
  * replaces: select_object -> extract_towers (utils/pcd_processing.py:508-522, 577-651: np.isin over the classes, open3d's
  *           cluster_dbscan(eps=10, min_points=300) over the tower points of a whole scan and a pandas group-by, on the

@@ -107,6 +107,9 @@ SYMBOLS = {
     "sn_crop_count": (c_int, [_P, ctypes.c_int64, _P, _P, _I, _P, ctypes.c_size_t, _P, _P]),
     "sn_crop_scatter": (c_int, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P, _P,
                                 _P]),
+    "sn_crop_census_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I, _I]),
+    "sn_census_chunk_points": (c_int, []),
+    "sn_crop_census": (c_int, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _I, _P, ctypes.c_size_t, _P, _P, _P]),
     "sn_points_select_chunk_points": (c_int, []),
     "sn_dbscan_chunk_points": (c_int, []),
     "sn_points_select_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
@@ -132,6 +135,7 @@ SN_CURVE_MAX_THRESHOLDS = 255
 SN_TOWER_NSTAT, SN_TOWER_LAUNCHES, SN_TOWER_MAX_RADIUS = 12, 6, 10
 SN_TSCORE_MAX_ROWS, SN_TSCORE_NTOTAL = 1024, 8
 SN_CROP_DISC, SN_CROP_BOX = 0, 1
+SN_CENSUS_MAX_WATCH = 16
 SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
 OCC_MAX_WORDS = 16 * 1024
 
@@ -1399,6 +1403,46 @@ def crop_scatter(pts: torch.Tensor, labels: Optional[torch.Tensor], regions: tor
                                 _ptr(out_labels, torch.float64, "out_labels"), _ptr(out_src, torch.int64, "out_src"),
                                 _stream())
     _check(rc, "sn_crop_scatter")
+
+
+# --------------------------------------------------------------------------- #
+def census_chunk_points() -> int:
+    """sn_census_chunk_points: points per workgroup of the census kernel (host only)."""
+    return int(load().sn_census_chunk_points())
+
+
+def crop_census_ws_bytes(n: int, K: int, C: int) -> int:
+    """sn_crop_census_ws_bytes: scratch bytes of crop_census over n points, K regions and C watch ranges (host only)."""
+    need = int(load().sn_crop_census_ws_bytes(int(n), int(K), int(C)))
+    if need == 0:
+        raise HipLibraryError(f"sn_crop_census serves no scan of {n} points with {K} regions and {C} watch ranges "
+                              f"(1 <= n <= 2^36, 1 <= K <= 65536, 0 <= C <= {SN_CENSUS_MAX_WATCH})")
+    return need
+
+
+@_on_tensor_device
+def crop_census(pts: torch.Tensor, labels: Optional[torch.Tensor], regions: torch.Tensor, kinds: Optional[torch.Tensor],
+                watch: Optional[torch.Tensor], ws: torch.Tensor, counts: torch.Tensor,
+                label_range: Optional[torch.Tensor]) -> None:
+    """sn_crop_census: pts [n,3] f64, labels [n] f64 | None, regions [K,4] f64, kinds [K] i32 | None, watch [C,2] f64 | None
+    (C = 0) -> counts [K, 2 + C] i64 and label_range [K,2] f64 (iff labels), with `ws` (crop_census_ws_bytes) all
+    caller-owned.  One memset node and two launches, no allocation, no synchronisation."""
+    n, K = _crop_head(pts, regions, kinds)
+    C = 0 if watch is None else int(watch.shape[0])
+    if watch is not None and (watch.dim() != 2 or watch.shape[1] != 2 or C == 0):
+        raise HipLibraryError(f"watch must be [C, 2] with C >= 1, or None (got {tuple(watch.shape)})")
+    if labels is not None and labels.numel() != n:
+        raise HipLibraryError("labels and pts disagree in length")
+    if counts.numel() != K * (2 + C):
+        raise HipLibraryError("counts must hold K * (2 + C) entries")
+    if label_range is not None and label_range.numel() != 2 * K:
+        raise HipLibraryError("label_range must hold 2 * K entries")
+    rc = load().sn_crop_census(_ptr(pts, torch.float64, "pts"), _ptr(labels, torch.float64, "labels"), n,
+                               _ptr(regions, torch.float64, "regions"), _ptr(kinds, torch.int32, "kinds"), K,
+                               _ptr(watch, torch.float64, "watch"), C, _ptr(ws, None, "ws"),
+                               ws.numel() * ws.element_size(), _ptr(counts, torch.int64, "counts"),
+                               _ptr(label_range, torch.float64, "label_range"), _stream())
+    _check(rc, "sn_crop_census")
 
 
 # --------------------------------------------------------------------------- #

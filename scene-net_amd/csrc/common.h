@@ -127,6 +127,17 @@ __device__ __forceinline__ void sticky_latch(int32_t* sticky, int code, int a, i
     }
 }
 
+// Order-preserving map of an fp64 to a uint64 (a < b  <=>  enc(a) < enc(b) for values that are not NaN; -0.0 sorts below
+// +0.0) and back: what lets integer atomicMin / atomicMax reduce fp64 minima and maxima (K1's boxes, K12's label range).
+__device__ __forceinline__ unsigned long long enc_f64(double d) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double dec_f64(unsigned long long u) {
+    u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
+    return __longlong_as_double((long long)u);
+}
+
 // One int of device memory per call (the flag an int8 launch leaves for the gated fp32 launch enqueued behind it, dynamic
 // tile tickets): from a recycled ring for eager launches, from a never-recycled pool while `stream` is capturing
 // (cabi.hip).  nullptr if the pool cannot be allocated.

@@ -131,14 +131,8 @@ __device__ __forceinline__ void for_each_point(const double* __restrict__ pts, l
 }
 
 // ---------------------------------------------------------------- order-preserving double <-> u64
-__device__ __forceinline__ unsigned long long enc_f64(double d) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dec_f64(unsigned long long u) {
-    u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
-    return __longlong_as_double((long long)u);
-}
+using sn::enc_f64;   // common.h
+using sn::dec_f64;
 
 __global__ void bbox_init_kernel(unsigned long long* enc, int B) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
