@@ -21,8 +21,10 @@ FLAGS_crops := -ffp-contract=off
 FLAGS_dbscan := -ffp-contract=off
 # tower_score.hip: centroids, means and distances are fp64 operations rounded once each, in numpy's order
 FLAGS_tower_score := -ffp-contract=off
+# las.hip: a coordinate is (double)X * scale + offset with the product and the sum rounded once each, as numpy rounds them
+FLAGS_las := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

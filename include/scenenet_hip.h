@@ -999,6 +999,44 @@ int sn_tower_match(const double* agg, const int32_t* n_agg, const int32_t* statu
                    int64_t* totals, double* dist_total, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K13 -- LAS decode: the point records of an uncompressed .las file -> the scan layout of K9, K10 and K12.
+ * replaces: las_to_numpy (utils/pcd_processing.py:99-120) behind lp.read(filename) in build_data_samples
+ *           (core/datasets/ts40k.py:73-86): laspy's scaled views of X, Y, Z (int32 * scale + offset in fp64),
+ *           np.vstack((las.x, las.y, las.z)).transpose() and np.array(las.classification), all on one host core before
+ *           the scan can be uploaded.  Here the record bytes go host-to-device as the file holds them.
+ *
+ * records:  n records of record_length bytes each, on the device, at ANY byte alignment.  All fields little-endian.
+ * X, Y, Z:  int32 at bytes 0, 4 and 8 of a record.
+ * pts:      [n,3] f64,  pts[i] = (fl(fl((double)X * sx) + ox), fl(fl((double)Y * sy) + oy), fl(fl((double)Z * sz) + oz)):
+ *           the conversion is exact, the product and the sum are each rounded once and never contracted -- numpy's
+ *           `X * scale + offset`, which is what laspy's scaled view computes.
+ * classes:  [n] f64 (nullable).  Point formats 0..5: (double)(byte 15 & 31) -- the synthetic, key-point and withheld bits
+ *           are dropped, as las.classification drops them.  Point formats 6..10: (double)(byte 16).
+ * hist:     [256] i64 (nullable), ACCUMULATED, not cleared: hist[c] gains the number of records whose class is c.  The
+ *           caller zeroes it, so the chunks of one file add up.
+ * Bytes of a record beyond those fields are never interpreted.
+ * ------------------------------------------------------------------------- */
+
+/* Records per workgroup and pass of the decode kernel (256): host only -- lets a test put its sizes on the seams. */
+int sn_las_chunk_records(void);
+
+/* scale, offset: HOST pointers to three doubles each, read during the call only (they travel as kernel arguments: a
+ * captured replay keeps those of capture time).  One launch on `stream`: record_length <= 80 stages a workgroup's byte
+ * span in LDS with aligned 16-byte loads issued one pass ahead, longer records are read as aligned dwords; neither issues
+ * a byte-wide global load.  The kernel may READ, and never writes, the rest of the aligned 16-byte granules that hold the first and the last
+ * byte of `records` (such a granule lies in the same page as a valid byte).  Nothing beyond point n - 1 is written; pts
+ * and classes are stored 16 bytes at a time wherever the address allows.  The histogram is summed per workgroup in LDS
+ * and added with 64-bit integer atomics: it does not depend on scheduling.  No allocation, no synchronisation: capturable.
+ * All byte arithmetic is 64-bit: n * record_length may exceed 2^31.
+ * SN_ERR_INVALID_ARG: a null records / pts / scale / offset, n <= 0, point_format outside 0..10, record_length below the
+ * format's standard length (20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67 for formats 0..10) or above 65535, a scale or
+ * offset that is not finite, pts / classes / hist not 8-byte aligned;  SN_ERR_UNSUPPORTED: n > 2^36.  All checked before
+ * the launch. */
+int sn_las_decode(const void* records, int64_t n, int point_format, int record_length, const double scale[3],
+                  const double offset[3], double* pts, double* classes, int64_t* hist, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ from .crops import (ScanCrops, crop_at_locations, crop_regions, crop_tower_radiu
 from .clusters import PointClusters, cluster_points, crop_two_towers_samples, extract_towers, select_object
 from .census import (RegionCensus, accept_kinds, crop_accepted, crop_ground_samples, crop_pole_slabs, pole_radius_samples,
                      region_census, scan_has_class, slab_regions, watch_equal, watch_trunc)
+from .las import (LasHeader, LasReader, LasScan, build_data_samples, las_to_numpy, plan_chunks, read_las, read_las_header,
+                  split_slices)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss, GENEO_Loss,
                          GENEO_Tversky_Loss, TverskyLoss, WeightedMSE)
 
@@ -36,6 +38,7 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "tower_centroids", "get_tower_proposals", "compute_euc_dists", "tower_detection_values", "ScanCrops", "crop_regions", "crop_at_locations",
            "crop_tower_radius", "crop_two_towers", "crop_tower_samples", "lattice_regions", "merge_to_scan", "PointClusters", "cluster_points", "select_object", "extract_towers",
            "crop_two_towers_samples", "RegionCensus", "region_census", "watch_equal", "watch_trunc", "accept_kinds", "crop_accepted",
-           "slab_regions", "crop_ground_samples", "crop_pole_slabs", "pole_radius_samples", "scan_has_class", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
+           "slab_regions", "crop_ground_samples", "crop_pole_slabs", "pole_radius_samples", "scan_has_class", "LasHeader", "LasReader", "LasScan",
+           "read_las_header", "read_las", "las_to_numpy", "build_data_samples", "plan_chunks", "split_slices", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE"]

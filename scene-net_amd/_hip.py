@@ -122,6 +122,8 @@ SYMBOLS = {
                                           _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _I, _I, _P]),
     "sn_tower_centroids": (c_int, [_P, _P, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    "sn_las_chunk_records": (c_int, []),
+    "sn_las_decode": (c_int, [_P, ctypes.c_int64, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sn_tower_match": (c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
@@ -1548,3 +1550,36 @@ def dbscan_points(pts: torch.Tensor, sel: Optional[torch.Tensor], n_sel: Optiona
     else:
         rc = load().sn_dbscan_points_launches(*head, int(launches[0]), int(launches[1]), _stream())
     _check(rc, "sn_dbscan_points")
+
+
+# --------------------------------------------------------------------------- #
+def las_chunk_records() -> int:
+    """sn_las_chunk_records: records per workgroup and pass of the LAS decode kernel (host only)."""
+    return int(load().sn_las_chunk_records())
+
+
+@_on_tensor_device
+def las_decode(records: torch.Tensor, n: int, point_format: int, record_length: int, scale: Sequence[float],
+               offset: Sequence[float], pts: torch.Tensor, classes: Optional[torch.Tensor] = None,
+               hist: Optional[torch.Tensor] = None) -> None:
+    """sn_las_decode: records, a uint8 tensor at ANY byte address that holds n records of record_length bytes -> pts [n,3]
+    f64, classes [n] f64 | None, hist [256] i64 | None (ACCUMULATED: the caller zeroes it), all caller-owned and written in
+    place; pts / classes may be larger, nothing beyond point n - 1 is touched.  One launch, no allocation, no
+    synchronisation."""
+    n, record_length = int(n), int(record_length)
+    if records.dtype != torch.uint8 or records.dim() != 1:
+        raise HipLibraryError("records must be a one-dimensional uint8 tensor (the file's bytes as they are)")
+    if n > 0 and records.numel() < n * record_length:
+        raise HipLibraryError(f"records holds {records.numel()} bytes, {n} records of {record_length} need more")
+    if n > 0 and (pts.numel() < 3 * n or (classes is not None and classes.numel() < n)):
+        raise HipLibraryError("pts / classes are smaller than the records they are to hold")
+    if hist is not None and hist.numel() != 256:
+        raise HipLibraryError("hist must hold 256 counts")
+    if len(scale) != 3 or len(offset) != 3:
+        raise HipLibraryError("scale and offset have 3 entries each")
+    sc = (ctypes.c_double * 3)(*[float(v) for v in scale])
+    of = (ctypes.c_double * 3)(*[float(v) for v in offset])
+    rc = load().sn_las_decode(_ptr(records, torch.uint8, "records"), n, int(point_format), record_length,
+                              ctypes.cast(sc, c_void_p), ctypes.cast(of, c_void_p), _ptr(pts, torch.float64, "pts"),
+                              _ptr(classes, torch.float64, "classes"), _ptr(hist, torch.int64, "hist"), _stream())
+    _check(rc, "sn_las_decode")
