@@ -134,7 +134,11 @@ int sn_device_count(void);
  *   "corr_sparse_tile_bytes" (0 .. 2048, default 0): input bytes per job of that gather (0: 2048, the maximum).
  *   "conv_i8z_inject_fault" (switch, default 0): TEST HOOK.  1 = the next z-walk launches never report plane 0's first raw
  *       rows as landed, so a dependency spin gives up (~0.5 s per launch): the way to see the loud failure path -- NaN
- *       outputs and the sticky device status -- on the product build (tests/test_gpu_conv_zwalk.py). */
+ *       outputs and the sticky device status -- on the product build (tests/test_gpu_conv_zwalk.py).
+ *   "conv_i8z_dense" (switch, default 0): the z-walk (sn_conv_bank_prepared[_served]) skips every round whose operand
+ *       window -- 9 planes x 9 halo rows -- holds no set voxel and stores the epilogue's constant instead; the results are
+ *       the same bit for bit (banks with a non-finite coefficient are never skipped), the run time depends on the data.
+ *       1 = every round runs: the A/B switch, and the dense-convention figure benchmarks quote beside the default one. */
 int sn_set_option(const char* name, int value);
 int sn_get_option(const char* name);
 
@@ -244,6 +248,9 @@ int sn_conv_prep_verdict_offset(void);
  * not silent: it latches the sticky device status (code 1 / 3, above), and the z-walk overwrites its workgroup's outputs
  * with NaN.  Synchronises the device. */
 int sn_conv_i8_spin_timeouts(unsigned long long* count);
+/* Diagnostics: rounds the z-walk ran [0] and skipped because their operand window was empty [1] (see "conv_i8z_dense"), all
+ * launches of this process on the device.  Each workgroup adds its sums once, at its end.  Synchronises the device. */
+int sn_conv_i8z_round_counts(unsigned long long* counts2);
 /* Diagnostics: how many workgroups of the one-pass voxelisation kernel (sn_voxel_occupancy_fused[_bank] at grids whose bitmap
  * fits one workgroup) ever gave up the bounded wait of the box exchange and took their tile's box from the points themselves
  * -- the same bits, one more pass over the tile.  0 in normal use; every workgroup with option voxel_onepass_spin = 0.

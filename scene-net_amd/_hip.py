@@ -46,6 +46,7 @@ SYMBOLS = {
     "sn_conv_bank_prepared_served": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "sn_conv_prep_verdict_offset": (c_int, []),
     "sn_conv_i8_spin_timeouts": (c_int, [_P]),
+    "sn_conv_i8z_round_counts": (c_int, [_P]),
     "sn_voxel_onepass_giveups": (c_int, [_P]),
     "sn_launch_timing_events": (c_int, [_P, _P]),
     "sn_conv_fused": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
@@ -236,6 +237,15 @@ def conv_i8_spin_timeouts() -> int:
     buf = (ctypes.c_ulonglong * 1)()
     _check(load().sn_conv_i8_spin_timeouts(ctypes.cast(buf, ctypes.c_void_p)), "sn_conv_i8_spin_timeouts")
     return int(buf[0])
+
+
+def conv_i8z_round_counts() -> Tuple[int, int]:
+    """(rounds run, rounds skipped) by the z-walk contraction since the library was loaded, on the current device: a round
+    whose operand window holds no set voxel is skipped unless option conv_i8z_dense is 1; synchronises
+    (sn_conv_i8z_round_counts)."""
+    buf = (ctypes.c_ulonglong * 2)()
+    _check(load().sn_conv_i8z_round_counts(ctypes.cast(buf, ctypes.c_void_p)), "sn_conv_i8z_round_counts")
+    return int(buf[0]), int(buf[1])
 
 
 def voxel_onepass_giveups() -> int:

@@ -45,6 +45,7 @@ enum Opt {
     kOptCorrDense,
     kOptCorrSparseTileBytes,
     kOptConvI8zInjectFault,
+    kOptConvI8zDense,
     kOptCount
 };
 // A relaxed atomic load.  An option with a variable reads it ONCE, at the first look (never per call: an environment

@@ -306,6 +306,7 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
     z.tol = s4.tol;
     z.route = route;
     z.dbg = sn::option(sn::kOptConvI8zInjectFault) ? 1 : 0;
+    z.dense = sn::option(sn::kOptConvI8zDense) ? 1 : 0;
     z.served = assume_served ? 1 : 0;
     z.sticky = sn::sticky_device_ptr(stream);
     s4.sticky = z.sticky;
@@ -328,6 +329,12 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_seg = ns; }
     }
     if (best_cost < 0) return 1;
+    if (!z.dense && SN_I8Z_SKIP_NSEG > 0 && SN_I8Z_SKIP_NSEG <= max_seg &&
+        (ncol * SN_I8Z_SKIP_NSEG + cus - 1) / cus <= kZMaxJobs) {
+        best_seg = SN_I8Z_SKIP_NSEG;
+        z.deal = 1;
+        z.deal_shift = SN_I8Z_SKIP_SHIFT;
+    }
     z.LZ = (Z + best_seg - 1) / best_seg;
     z.nseg = (Z + z.LZ - 1) / z.LZ;
     z.PL = z.LZ + 8;
@@ -473,6 +480,15 @@ extern "C" int sn_conv_i8_path_counts(unsigned long long* counts3) {
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fold_counts), sizeof(h)) != hipSuccess)
         return sn::check_launch("sn_conv_i8_path_counts");
     counts3[0] = h[0]; counts3[1] = h[1]; counts3[2] = h[2];
+    return SN_OK;
+}
+
+extern "C" int sn_conv_i8z_round_counts(unsigned long long* counts2) {
+    if (!counts2) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_i8z_round_counts: null pointer");
+    unsigned long long h[2] = {0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_zwalk_rounds), sizeof(h)) != hipSuccess)
+        return sn::check_launch("sn_conv_i8z_round_counts");
+    counts2[0] = h[0]; counts2[1] = h[1];
     return SN_OK;
 }
 

@@ -36,6 +36,28 @@
 // Ring arithmetic: plane u of the workgroup's plane stream (job k = u / PL, p = u % PL: grid plane zs_k - 4 + p) lives in
 // slot u & 15 of both rings.  Output o of job k needs planes k PL + o .. + 8; its four rounds ride on slot
 // k PL + o + kZD.  A fold pass at slot s overwrites plane s - 16, whose readers rode on slots s - 14 .. s - 6.
+//
+// EMPTY WINDOWS (round 6).  The input is LiDAR occupancy: a few per cent of the voxels are set, and a round whose operand
+// window -- 9 planes x 9 halo rows x the column's 96 halo bytes in y -- holds no set voxel has twelve accumulators that are
+// exactly 0.  The walk does not run such a round:
+//   * the fold pass has row 4 xr + q of its plane in registers (lane (q, n): the three raw dwords R0 R1 R2, i.e. the y window
+//     of that lane's four outputs +- 4).  A row is NON-EMPTY when (R0 | R1 | R2) != 0 in any of its 16 lanes: one ballot per
+//     pass, four row bits (scalar: s_quadmask twice), written by one lane as BYTE xr of the dword rowmask[u & 15] (bit q of byte xr = row 4 xr + q; four
+//     passes by four waves never read-modify-write each other).  The store goes out ahead of the pass's folded[] report.
+//     The rule is CONSERVATIVE: a row's bit covers the whole y extent the 16 lanes read (y0 - 4 .. y0 + 67, clipped to the
+//     grid), and the 16 rows x0 - 4 .. x0 + 11, halo included, so a voxel that only a neighbouring column's or y tile's
+//     outputs need still sets it.  It never calls a window empty that is not.
+//   * a ticket reads the nine mask dwords of its planes in ONE ds_read_b32 (lanes 0..8, the counter index its dependency
+//     check formed) behind the check and ahead of its passes -- guarded like the ring: valid once folded[] of the nine slots
+//     is complete, protected from the fold that reuses a slot by the read[] report (hand-over 3), which every path issues
+//     behind a wait for the read's return (a ticket without a round reads too and drops the value).  A round of x-rows
+//     h .. h + kH - 1 is empty when no lane's dword has one of the row bits h .. h + kH + 7.
+//   * an empty round issues no operand read, no weight read and no MFMA; it stores what finish_round would store for
+//     all-zero accumulators (zero_round: + 0.0 activations; for `out` the same operations from e = + 0.0 on: the head & 1
+//     load-and-add, the head & 2 relu_tanh).  That equals the full epilogue bit for bit iff coefficient x 0 = + 0, so the
+//     prologue allows skipping (can_skip, workgroup-uniform) only if all 16 entries of scale, lamsc and lamhi are finite
+//     (scale not negative) and sn_set_option("conv_i8z_dense") is 0; otherwise every round runs, NaN / inf propagate.
+//   sn_conv_i8z_round_counts: rounds run / skipped, summed per workgroup in LDS and added once at its end.
 
 constexpr int kZTX = 8;                        // output x-rows per column
 constexpr int kZRows = kZTX + 8;               // halo rows per plane
@@ -57,6 +79,14 @@ constexpr int kZYqRow = 256, kZYqPlane = kZRows * kZYqRow;   // 16 lanes x 16 B;
 constexpr int kZYcRow = 64, kZYcPlane = kZRows * kZYcRow + 32;   // 264 dwords: planes 2 apart (lane groups 0/1, 2/3) and
                                                                  // planes -14 apart (ring wrap) are 16 banks apart (mod 32)
 constexpr int kZMaxJobs = 256;                 // jobs per workgroup (job table in LDS)
+// Skip mode only: cut every column into this many z segments and deal segment sg of column xt to the workgroup of column
+// xt + SN_I8Z_SKIP_SHIFT sg, so that a workgroup's work comes from several columns (0: the plan of the dense walk).
+#ifndef SN_I8Z_SKIP_NSEG
+#define SN_I8Z_SKIP_NSEG 0
+#endif
+#ifndef SN_I8Z_SKIP_SHIFT
+#define SN_I8Z_SKIP_SHIFT 0
+#endif
 #ifndef SN_I8Z_AHEAD
 #define SN_I8Z_AHEAD 2                         // operand units are requested this many pieces before their fold
 #endif
@@ -83,7 +113,13 @@ struct ZShape {
                                   // must not return quietly -- it poisons its outputs and latches the sticky status
     int32_t* sticky;              // the device's sticky status words (host-pinned, cabi.hip: sn::sticky_device_ptr)
     int dbg;
+    int dense;                    // sn_set_option("conv_i8z_dense"): run every round, whatever its window holds
+    int deal, deal_shift;         // jobs in segment-major order, segment sg of column (b, yt, xt) dealt as column xt + shift sg
+                                  // (mod nxt): a workgroup's segments come from different columns (SN_I8Z_SKIP_NSEG)
 };
+
+// diagnostics (sn_conv_i8z_round_counts): rounds the walk ran / skipped (empty operand window), all launches since load
+__device__ unsigned long long g_zwalk_rounds[2] = {0ull, 0ull};
 
 __device__ __forceinline__ int zjob_id(const ZShape& z, int wg, int k, int grid) {
     const int base = k * grid;
@@ -195,6 +231,82 @@ __device__ __forceinline__ void finish_round1(const SH& s, const TileCoord& c, i
     }
 }
 
+// What finish_round1 / finish_round store for a round whose accumulators are all zero, when every coefficient is finite
+// (can_skip): val = fma(0, 65536, 0) = + 0 and + 0 x scale = + 0 (scale >= 0); the packed FMAs give lam x 0 + (+ 0) = + 0
+// whatever lam's sign, the lane sums + 0 + + 0 = + 0; from e = + 0 on the operations are the epilogue's own (the zero is made
+// opaque so that they are issued, not folded).
+template <typename OT>
+__device__ __forceinline__ void zero_act_row(OT* o) {
+    if constexpr (sizeof(OT) == 4) {
+        *reinterpret_cast<float4*>(o) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    } else {
+        reinterpret_cast<double2*>(o)[0] = make_double2(0.0, 0.0);
+        reinterpret_cast<double2*>(o)[1] = make_double2(0.0, 0.0);
+    }
+}
+template <typename OT, typename SH>
+__device__ __forceinline__ void zero_round1(const SH& s, const TileCoord& c, int lx, int n, int q, int col,
+                                            OT* __restrict__ act, OT* __restrict__ out, size_t V) {
+    const int gz = c.z0;
+    const int gx = c.x0 + lx;
+    if (gz >= s.Z || gx >= s.X) return;
+    const int gy4 = c.y0 + 4 * n;
+    if (act && gy4 < s.Y) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int g = 4 * q + r;
+            if (g < s.G) zero_act_row(act + ((size_t)c.b * s.Gtot + s.g0 + g) * V + ((size_t)gz * s.X + gx) * s.Y + gy4);
+        }
+    }
+    if (out) {
+        const int gy = c.y0 + col;
+        if (gy < s.Y) {
+            OT* row = out + ((size_t)c.b * V + ((size_t)gz * s.X + gx) * s.Y + c.y0);
+            OT* o = row + (unsigned)col;
+            float t0 = 0.0f;
+            asm volatile("" : "+v"(t0));
+            if (s.head & 1) t0 += (float)load_now(o);
+            if (s.head & 2) t0 = relu_tanh(t0);
+            *o = (OT)t0;
+        }
+    }
+}
+// (two x-rows: finish_round's stores)
+template <typename OT, typename SH>
+__device__ __forceinline__ void zero_round2(const SH& s, const TileCoord& c, int lx, int n, int q, OT* __restrict__ act,
+                                            OT* __restrict__ out, size_t V) {
+    const int gz = c.z0;
+    if (gz >= s.Z) return;
+    const int gy4 = c.y0 + 4 * n;
+    if (act && gy4 < s.Y) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int gx = c.x0 + lx + h;
+            if (gx < s.X) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int g = 4 * q + r;
+                    if (g < s.G) zero_act_row(act + ((size_t)c.b * s.Gtot + s.g0 + g) * V + ((size_t)gz * s.X + gx) * s.Y + gy4);
+                }
+            }
+        }
+    }
+    if (out) {
+        const int h = q >> 1;
+        const int gx = c.x0 + lx + h, gy = gy4 + 2 * (q & 1);
+        if (gx < s.X && gy < s.Y) {
+            OT* row = out + ((size_t)c.b * V + ((size_t)gz * s.X + (c.x0 + lx)) * s.Y + c.y0);
+            OT* o = row + (unsigned)(h * s.Y + 4 * n + 2 * (q & 1));
+            float t0 = 0.0f, t1 = 0.0f;
+            asm volatile("" : "+v"(t0), "+v"(t1));
+            if (s.head & 1) { t0 += (float)load_now(o); t1 += (float)load_now(o + 1); }
+            if (s.head & 2) { t0 = relu_tanh(t0); t1 = relu_tanh(t1); }
+            if constexpr (sizeof(OT) == 4) *reinterpret_cast<float2*>(o) = make_float2(t0, t1);
+            else *reinterpret_cast<double2*>(o) = make_double2((double)t0, (double)t1);
+        }
+    }
+}
+
 // LDS counter add by ONE lane, as the instruction it is: hipcc's atomic optimiser turns `if (lane == 0) atomic_add` into a
 // cross-lane aggregation (mbcnt, bcnt, a second exec dance: ~12 instructions per signal, four signals per ticket)
 // kTag names the hand-over in the ISA (a comment inside the asm block: `; @zw:add<kTag>`), for tools/zwalk_handover_audit.py:
@@ -247,12 +359,16 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     int4* chk = reinterpret_cast<int4*>(cnt + 128);                              // [64] the dependency check's lane roles
     int4* ltab = chk + 64;                                                       // [64] a lane's constants (n 16, q 256, 4 n + q, -)
     int4* stab = ltab + 64;                                                      // [16][4] ring offsets of (sigma & 15, lane group q)
-    uint8_t* raw = reinterpret_cast<uint8_t*>(stab + 64);                        // [16][16 rows][96 B]
+    uint32_t* rowmask = reinterpret_cast<uint32_t*>(stab + 64);                  // [16] non-empty rows of the plane in ring slot u & 15:
+                                                                                 // byte xr, bit q = row 4 xr + q (+ 64 B spare: the
+                                                                                 // rings stay 128-byte aligned)
+    uint8_t* raw = reinterpret_cast<uint8_t*>(rowmask + 32);                     // [16][16 rows][96 B]
     uint8_t* Yc = raw + kZRing * kZRawPlane;                                     // [16][16 rows][16 lanes] x 4 B (+ 32 B per plane)
     uint8_t* Yq = Yc + kZRing * kZYcPlane;                                       // [16][16 rows][16 lanes] x 16 B
     // counters: [0..15] folded[slot]: fold passes of the planes that lived there (4 per plane);
     //           [16..31] read[slot]: tickets of the slots s = slot (mod 16) that are through with their ring reads (kTPS per slot);
     //           [32..95] landed[pass][slot]: LDS-DMA passes arrived;  [96] ticket counter;  [97] asymmetric bank;  [98] a spin gave up
+    //           [99] can_skip;  [100] rounds run, [101] rounds skipped, [102] waves that have added theirs
     int* const ticket_ctr = cnt + 96;
 
 #ifdef SN_CONV_TIMING
@@ -314,9 +430,18 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     }
     if (tid < my_jobs) {
         int j = zjob_id(zs, (int)blockIdx.x, tid, grid);
-        const int xt = j % zs.nxt; j /= zs.nxt;
-        const int yt = j % zs.nyt; j /= zs.nyt;
-        const int sg = j % zs.nseg; j /= zs.nseg;
+        int xt, yt, sg;
+        if (zs.deal) {
+            const int ncol = zs.B * zs.nxt * zs.nyt;
+            sg = j / ncol; j -= sg * ncol;
+            xt = j % zs.nxt; j /= zs.nxt;
+            yt = j % zs.nyt; j /= zs.nyt;
+            xt = (xt + zs.deal_shift * sg) % zs.nxt;
+        } else {
+            xt = j % zs.nxt; j /= zs.nxt;
+            yt = j % zs.nyt; j /= zs.nyt;
+            sg = j % zs.nseg; j /= zs.nseg;
+        }
         jobtab[tid] = make_int4(j, xt * kZTX, yt * TY, sg * zs.LZ);
     }
     lds_barrier();
@@ -359,6 +484,13 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         const int n = ln & 15, q = ln >> 4;
         const uint32_t* p = reinterpret_cast<const uint32_t*>(raw + (u & 15) * kZRawPlane + (4 * xr + q) * (DW * 4) + (n + D0) * 4);
         const uint32_t R0 = p[0], R1 = p[1], R2 = p[2];
+        // which of the pass's four rows hold a set voxel: lane group q is row 4 xr + q (scalar arithmetic on the ballot)
+        const unsigned long long any = __builtin_amdgcn_ballot_w64((R0 | R1 | R2) != 0u);
+        // (s_quadmask: bit i = OR of the source's bits 4 i .. 4 i + 3; twice: bit q = OR of the 16 lanes of group q)
+        unsigned long long any4;
+        uint32_t rowbits;
+        asm("s_quadmask_b64 %0, %1" : "=s"(any4) : "s"(any) : "scc");
+        asm("s_quadmask_b32 %0, %1" : "=s"(rowbits) : "s"((uint32_t)any4) : "scc");
         uint4 f;
         f.x = R0 + __builtin_amdgcn_perm(R2, R1, 0x01020304u);
         f.y = __builtin_amdgcn_alignbyte(R1, R0, 1) + __builtin_amdgcn_perm(R2, R1, 0x02030405u);
@@ -366,6 +498,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         f.w = __builtin_amdgcn_alignbyte(R1, R0, 3) + __builtin_amdgcn_perm(R2, R1, 0x04050607u);
         *reinterpret_cast<uint4*>(Yq + (u & 15) * kZYqPlane + (4 * xr + q) * kZYqRow + n * 16) = f;
         *reinterpret_cast<uint32_t*>(Yc + (u & 15) * kZYcPlane + (4 * xr + q) * kZYcRow + n * 4) = R1;
+        if (lane == 0) reinterpret_cast<uint8_t*>(rowmask)[(u & 15) * 4 + xr] = (uint8_t)rowbits;   // (ahead of the folded[] report)
     };
 
     // ---- NaN over everything this workgroup owns in `out` / `act` (cold: a spin gave up, or a `served` launch declined)
@@ -427,14 +560,26 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             return;
         }
     }
-    if (tid < 16) {
-        const float ls = (out && tid < zs.G) ? lamhi[16 + tid] * scale[tid] : 0.0f;
-        lamsc[tid] = ls;
-        lamhi[tid] = 65536.0f * ls;
+    if (wave == 0) {
+        bool fin = true;
+        if (tid < 16) {
+            const float sc = scale[tid];
+            const float ls = (out && tid < zs.G) ? lamhi[16 + tid] * sc : 0.0f;
+            const float lh = 65536.0f * ls;
+            lamsc[tid] = ls;
+            lamhi[tid] = lh;
+            auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+            fin = finite(sc) && !(__float_as_uint(sc) >> 31) && finite(ls) && finite(lh);
+        }
+        // can_skip: an empty round's epilogue is a constant only if coefficient x 0 = + 0 for every coefficient
+        const bool all_fin = __builtin_amdgcn_ballot_w64(!fin) == 0ull;
+        if (lane == 0) cnt[99] = (all_fin && !zs.dense) ? 1 : 0;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (my_jobs == 0) return;
+    const bool can_skip = __builtin_amdgcn_readfirstlane(cnt[99]) != 0;
+    int n_run = 0, n_skip = 0;   // this wave's rounds (scalar)
     SN_ST(4);
 
     bool healthy = true;
@@ -489,6 +634,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         }
         SN_ZT(0, tz0);
         const unsigned long long tz1 = SN_ZNOW();
+        int midx;   // lanes 0..8: ring slot of plane sigma + i (the dependency check's counter index)
         // ---- everything this ticket depends on, in one LDS read: lane roles
         //   0..8   folded[plane sigma + i]   (round: its nine planes)           16..24  read[slot s - 14 + i]  (fold: the readers
         //   32..   landed[plane s][pass]     (fold: its raw rows)                        of the plane it overwrites)
@@ -499,6 +645,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             const int v = s + role.x;
             const int idx = ((v & 15) | role.y) + (role.z & (xr0 * 16));   // (bits 4, 5 of role.z: the landed counter of pass xr0)
             const int expect = ((role.z & have) && v >= 0) ? (((v >> 4) + 1) << role.w) : 0;
+            midx = idx;
             int spins = 0;
             while (true) {
                 // (an LDS read, spelled in its address space: through a generic volatile pointer hipcc emits a FLAT load with
@@ -532,6 +679,12 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         }
         SN_ZT(1, tz1);
         const unsigned long long tz2 = SN_ZNOW();
+        // the row masks of the ticket's nine planes (lanes 0..8; the other lanes read whatever their counter index points at
+        // in the words behind the masks and are cut from the ballot): guarded data, requested behind the spin exit and ahead
+        // of the ticket's passes, whose own LDS waits cover its latency.  Every ticket reads them (a ticket without a round
+        // drops the value) and every read[] report waits for the read's return first (`@zw:wait3`).
+        const uint32_t rmask = reinterpret_cast<const volatile __attribute__((address_space(3))) uint32_t*>(
+            (__attribute__((address_space(3))) uint32_t*)rowmask)[midx];
         if (has_dma) {
             dma_pass(sd, xr0, ln);
             pend = 32 + xr0 * 16 + (sd & 15);
@@ -546,6 +699,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         }
         SN_ZT(2, tz2);
         if (!has_round) {
+            asm volatile("; @zw:wait3\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
             lds_add_lane0<3>(&cnt[16 + (s & 15)], 1, lane);
             continue;
         }
@@ -555,6 +709,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         c.b = jr.b; c.x0 = jr.x0; c.y0 = jr.y0; c.z0 = jr.zs + o;
         const int lx = kH * kR * tk;   // the ticket's first x-row
         if (c.z0 >= zs.Z || c.x0 + lx >= zs.X) {   // (a last segment shorter than LZ; x-rows past the grid)
+            asm volatile("; @zw:wait3\n\ts_waitcnt lgkmcnt(0)" ::: "memory");   // (the mask read: nothing else was read)
             lds_add_lane0<3>(&cnt[16 + (s & 15)], 1, lane);
             continue;
         }
@@ -628,11 +783,37 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         // rounds of this ticket that lie inside the grid (x-rows past X end the ticket early)
         const int rows_left = zs.X - (c.x0 + lx);
         const int nvalid = rows_left >= kH * kR ? kR : (rows_left + kH - 1) / kH;
+        // which of the ticket's rounds have a set voxel in their window (wave-uniform): rows lx + rr kH .. + kH + 7 of the
+        // nine planes, as bits of the masks' layout (byte xr, bit q)
+        uint32_t hits[kR];   // lanes 0..8 with a row bit inside the window of round rr (scalar)
+#pragma unroll
+        for (int rr = 0; rr < kR; ++rr) {
+            const uint32_t w = ((1u << (8 + kH)) - 1u) << (lx + rr * kH);
+            uint32_t wb = (w & 0xfu) | ((w & 0xf0u) << 4) | ((w & 0xf00u) << 8) | ((w & 0xf000u) << 12);
+            asm("" : "+s"(wb));   // (one scalar operand: v_and + v_cmp per round)
+            hits[rr] = can_skip ? ((uint32_t)__builtin_amdgcn_ballot_w64((rmask & wb) != 0u) & 0x1ffu) : 1u;
+        }
         // The ticket's rounds run as a LOOP (not unrolled: one copy of the round's code, one round's registers -- [measured]
         // two unrolled rounds spilled 27 reloads into the loop and were no faster than one round per ticket); the six ring
         // addresses advance by kH rows per round.
 #pragma unroll 1
         for (int rr = 0; rr < nvalid; ++rr) {
+            if ((kR == 1 || rr == 0 ? hits[0] : hits[kR - 1]) == 0u) {
+                // an empty window: no operand read, no weight read, no MFMA.  The ticket's read[] report stays where it is
+                // (HAND-OVER 3): the mask read has returned (the verdict needed it), and a round of this ticket that ran
+                // has waited for its ring reads before its last MFMA step's operands were formed.
+                if (rr == nvalid - 1) {
+                    asm volatile("; @zw:wait3\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+                    lds_add_lane0<3>(&cnt[16 + (s & 15)], 1, lane);
+                }
+                if constexpr (kH == 2) zero_round2<OT>(zs, c, lx + rr * kH, n, q, act, out, V);
+                else zero_round1<OT>(zs, c, lx + rr * kH, n, q, LT.z, act, out, V);
+                ++n_skip;
+                yqA += kH * kZYqRow; yqB += kH * kZYqRow; yq8 += kH * kZYqRow;
+                ycA += kH * kZYcRow; ycB += kH * kZYcRow; yc8 += kH * kZYcRow;
+                continue;
+            }
+            ++n_run;
             constexpr int ro = 0;
             // A step has 3 kH operand units u = (row j = u / kH, x-row h = u % kH) and kH centre transposes: 4 kH pieces,
             // built behind the 4 kH MFMA groups of the step before; unit u's quads are requested kAhead pieces before its fold.
@@ -758,6 +939,17 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         asm volatile("; @zw:wait1\n\ts_waitcnt vmcnt(0)" ::: "memory");
         signal_passes(pend);
     }
+    // ---- round counts: every wave adds its own to the workgroup's LDS words, the last one to do so adds the sums to the
+    // device's (one pair of global atomics per workgroup; a wave's DS operations reach the LDS in order)
+    if (lane == 0) {
+        const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int*)(cnt + 100);
+        asm volatile("ds_add_u32 %0, %1\n\tds_add_u32 %0, %2 offset:4" ::"v"(a), "v"(n_run), "v"(n_skip) : "memory");
+        if (atomicInc(reinterpret_cast<unsigned*>(cnt + 102), 0xffffffffu) == (unsigned)kW - 1u) {
+            const volatile __attribute__((address_space(3))) int* tot = (__attribute__((address_space(3))) int*)cnt;
+            atomicAdd(&g_zwalk_rounds[0], (unsigned long long)(unsigned)tot[100]);
+            atomicAdd(&g_zwalk_rounds[1], (unsigned long long)(unsigned)tot[101]);
+        }
+    }
     // ---- a wave of this workgroup gave up: nothing the workgroup wrote can be trusted.  Every wave that is still alive gets
     // here (the flag ends every spin; a barrier does not wait for waves that have ended), its own stores are out (vmcnt),
     // and together they overwrite the workgroup's outputs with NaN.  sn_conv_i8_spin_timeouts counts the waves.
@@ -792,7 +984,7 @@ __global__ __launch_bounds__(kThreads) void conv_i8_fallback_kernel(const uint8_
 
 size_t lds_bytes_zwalk() {
     return (size_t)kFoldSteps * 3 * 64 * 16 + (size_t)kZMaxJobs * 16 + 64 * 4 + 128 + 128 * 4 + 64 * 16 + 2 * 64 * 16 +
-           (size_t)kZRing * (kZRawPlane + kZYcPlane + kZYqPlane) + 16;
+           32 * 4 + (size_t)kZRing * (kZRawPlane + kZYcPlane + kZYqPlane) + 16;
 }
 
 // u / d == mulhi(u, magic) for all 0 <= u <= umax?  (magic = floor(2^32 / d) + 1; checked exhaustively: umax is small)

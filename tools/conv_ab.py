@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """A/B of the three forms of K3' (folded kernel vs stride-4 kernel vs four-copy kernel) and of the guard's gated fp32 launch, interleaved
 rounds in ONE process on the bench's C2 batch (cdna_hip_programming.md rule 24).
-    python tools/conv_ab.py [--rounds 5] [--iters 40] [--batch 32] [--grid 64]"""
+    python tools/conv_ab.py [--rounds 5] [--iters 40] [--batch 32] [--grid 64]
+    python tools/conv_ab.py --skip      the z-walk with and without its empty-window skip (sn_set_option "conv_i8z_dense"),
+                                        a dense / skip pair of rows on the C2 batch, on random 50 % occupancy (no window is
+                                        empty: the price of the check) and on an all-zero batch (the floor of a launch that
+                                        skips every round), with the rounds run / skipped of one launch"""
 import argparse
 import os
 import sys
@@ -24,6 +28,7 @@ def main():
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--points", type=int, default=100_000)
     ap.add_argument("--random-occ", type=float, default=0.0, help="random occupancy of this density instead of tiles")
+    ap.add_argument("--skip", action="store_true", help="dense / skip rows of the z-walk on three inputs")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     specs, names, lambdas, last = synthetic_bank_spec()
@@ -40,6 +45,8 @@ def main():
                                  occ_dtype=torch.bool).occ
 
     prep = _hip.conv_bank_prep(bank)
+    if args.skip:
+        return skip_ab(args, occ, bank, lam, prep)
     use_prep = [False]
 
     def run(n):
@@ -90,6 +97,59 @@ def main():
         med, mn = float(np.median(ts)), float(np.min(ts))
         print(f"{name:18s} median {med * 1e3:8.1f} us  min {mn * 1e3:8.1f} us  {flops / (med * 1e-3) / 1e12:7.1f} TFLOP/s "
               f"algorithmic  rounds {[round(t * 1e3, 1) for t in ts]}")
+
+
+def skip_ab(args, tiles_occ, bank, lam, prep):
+    """the prepared, served z-walk (what bench.py's step runs) with conv_i8z_dense = 1 and 0, interleaved"""
+    g = torch.Generator(device=tiles_occ.device).manual_seed(1)
+    inputs = {"C2 batch": tiles_occ,
+              "random 50 %": torch.rand(tiles_occ.shape, device=tiles_occ.device, generator=g) < 0.5,
+              "all zero": torch.zeros_like(tiles_occ)}
+    out = torch.empty(tiles_occ.shape, dtype=torch.float32, device=tiles_occ.device)
+    fn = _hip.load().sn_conv_bank_prepared_served
+    B, _, Z, X, Y = tiles_occ.shape
+    G = bank.shape[0]
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(x, n):
+        for _ in range(n):
+            rc = fn(x.data_ptr(), _hip.SN_OCC8, bank.data_ptr(), lam.data_ptr(), prep.data_ptr(), B, Z, X, Y, G, 9, 9, 9, None,
+                    out.data_ptr(), _hip.SN_F32, stream)
+            assert rc == 0, rc
+
+    rows = [(name, dense) for name in inputs for dense in (1, 0)]
+    res = {r: [] for r in rows}
+    counts, kept = {}, {}
+    t_spin = time.perf_counter()
+    while time.perf_counter() - t_spin < 0.3:
+        run(tiles_occ, 10)
+        torch.cuda.synchronize()
+    for r in range(args.rounds):
+        for name, dense in rows:
+            _hip.set_option("conv_i8z_dense", dense)
+            run(inputs[name], 5)
+            torch.cuda.synchronize()
+            if r == 0:
+                c0 = _hip.conv_i8z_round_counts()
+                run(inputs[name], 1)
+                c1 = _hip.conv_i8z_round_counts()
+                counts[(name, dense)] = (c1[0] - c0[0], c1[1] - c0[1])
+                kept[(name, dense)] = out.clone()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(inputs[name], args.iters)
+            e1.record()
+            torch.cuda.synchronize()
+            res[(name, dense)].append(e0.elapsed_time(e1) / args.iters)
+    _hip.set_option("conv_i8z_dense", 0)
+    for name, dense in rows:
+        ts = res[(name, dense)]
+        ran, skipped = counts[(name, dense)]
+        same = torch.equal(kept[(name, 0)].view(torch.int32), kept[(name, 1)].view(torch.int32))
+        print(f"{name:12s} {'dense' if dense else 'skip ':5s} median {float(np.median(ts)) * 1e3:8.1f} us  min {float(np.min(ts)) * 1e3:8.1f} us  "
+              f"rounds run {ran} skipped {skipped} ({100.0 * ran / max(1, ran + skipped):5.1f} % run)  same bits {same}  "
+              f"rounds {[round(t * 1e3, 1) for t in ts]}")
+    print(f"spin give-ups {_hip.conv_i8_spin_timeouts()}, device status {_hip.device_status()[0]}")
 
 
 if __name__ == "__main__":

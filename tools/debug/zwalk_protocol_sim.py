@@ -9,6 +9,10 @@ LDS-DMA is still in flight, which rounds are reading which planes -- and asserts
   RAW  a fold reads raw rows that have landed and belong to its plane;  a round reads folded rows of ITS nine planes
   WAR  an LDS-DMA does not overwrite raw rows whose fold has not run;  a fold does not overwrite a plane a round that is
        still in flight reads (checked when the round ENDS: its planes must still be in the ring)
+  MASK the row-mask word of a ring slot (one byte per fold pass: which of the pass's four rows hold a set voxel) is written
+       by the fold pass ahead of its folded[] report, read by every round ticket -- the nine words of its planes, in one
+       read behind the dependency check, whether the verdict then runs the round or skips it -- and overwritten 16 slots
+       later by the next owner's fold: a ticket must find the bytes of ITS nine planes
 
 Round 3's model checked completion and the two RAW cases under uniformly random interleavings; it had no notion of a round
 that is IN FLIGHT, so no schedule could show a WAR hazard.  This one (round 4) has, and its scheduler is adversarial: it
@@ -55,6 +59,7 @@ def simulate(my_jobs, LZ, kTPS, nwaves, seed, lag=3, dd=4, ordered_reads=True, s
     # ground truth
     raw = [[(sl if sl < npre else None) for sl in range(RING)] for _ in range(4)]   # raw[xr][slot] = plane | ('fly', plane) | None
     yring = [[None] * RING for _ in range(4)]                                         # yring[xr][slot] = plane
+    mask = [[None] * RING for _ in range(4)]                                          # mask[xr][slot] = plane whose rows byte xr describes
     fold_done = set()
     ticket = [0]
     waves = [dict(phase='claim', t=None, pend=None, planes=None, frozen=0) for _ in range(nwaves)]
@@ -165,9 +170,20 @@ def simulate(my_jobs, LZ, kTPS, nwaves, seed, lag=3, dd=4, ordered_reads=True, s
                     if raw[xr][s & 15] != s:
                         raise Hazard(f"fold of plane {s} pass {xr} reads raw rows holding {raw[xr][s & 15]}")
                     yring[xr][s & 15] = s
+                    mask[xr][s & 15] = s        # (the byte store goes out ahead of the folded[] report: same wave, DS order)
                     fold_done.add((s, xr))
                 folded[s & 15] += kPPT
-            if has_round and rng.random() >= skip_prob:
+            if has_round:
+                # the window check: every ticket with a round reads the mask words of its nine planes first (a ticket whose
+                # rows lie outside the grid leaves before that read: modelled as the odd tickets among the skipped ones)
+                ran = rng.random() >= skip_prob
+                if ran or (w['t'] & 1) == 0:
+                    for p in (sigma + i for i in range(9)):
+                        for xr in range(4):
+                            if mask[xr][p & 15] != p:
+                                raise Hazard(f"round of output {sigma} (slot {s}) reads the row mask of plane {p} pass {xr}: "
+                                             f"the word holds plane {mask[xr][p & 15]}")
+            if has_round and ran:
                 planes = [sigma + i for i in range(9)]
                 for p in planes:
                     for xr in range(4):

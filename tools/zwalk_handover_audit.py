@@ -7,15 +7,20 @@ counter and the data it publishes.  This script cross-compiles conv_i8s.hip to I
 the `; @zw:*` comments the source's asm statements carry, and checks, per instantiation:
 
   R1  consumer side: inside the ticket loop no ring / raw access (ds_read_b128, ds_read2_b32, ds_write_b128, LDS-DMA, or a
-      ds_read_b32 / ds_write_b32 outside the counter-and-table region) is placed between the ticket's claim and the
-      `@zw:spin_exit` marker -- nothing the dependency check guards is issued before the check has been passed.
+      ds_read_b32 / ds_write_b32 / ds_write_b8 outside the counter-and-table region) is placed between the ticket's claim
+      and the `@zw:spin_exit` marker -- nothing the dependency check guards is issued before the check has been passed.
+      The row masks (16 dwords behind the tables, K_TABLES_END .. K_MASK_END: written by the fold pass with ds_write_b8,
+      read by a ticket's rounds with one ds_read_b32) are guarded data like the rings.
   R2  the spin reads its counter with a DS instruction (never FLAT) and waits (lgkmcnt(0)) before it compares.
   R3  HAND-OVER 1 (LDS-DMA -> fold): every `@zw:add1` (landed) is preceded by a `@zw:wait1` (s_waitcnt vmcnt(0)) with no
       LDS-DMA and no branch target between them other than the lane-0 guard of the add.
   R4  HAND-OVER 2 (fold -> rounds): every `@zw:add2` (folded) follows the fold pass's ds_write_b128 and ds_write_b32 in the
-      same straight-line region, with no other DS write after it before the region ends.
+      same straight-line region, with no other DS write after it before the region ends; the pass's row-mask byte
+      (ds_write_b8) goes out ahead of the add as well.
   R5  HAND-OVER 3 (rounds -> fold): every `@zw:add3` (read) that ends a round is preceded by `@zw:wait3`
-      (s_waitcnt lgkmcnt(0)) with no DS read between the wait and the add.
+      (s_waitcnt lgkmcnt(0)) with no DS read between the wait and the add.  Every ticket reads its row masks behind the
+      spin exit, so EVERY read report has such a wait directly above: the one behind the MFMAs of a ticket's last round
+      (exactly one), and those of a ticket without a round, of a ticket outside the grid and of a round whose window is empty.
   R6  every LDS-DMA sits in the asm block that saves, sets and restores M0 (s_mov m0 / s_nop 0 / load / s_mov m0).
   R7  no FLAT memory instruction in the kernel, and no scratch access inside the ticket loop of the instantiations that are
       launched by default (a spill reload inside the loop would wait on vmcnt for the wave's LDS-DMA).
@@ -34,6 +39,7 @@ SRC = [os.path.join(ROOT, "scene-net_amd", "csrc", f) for f in
 # LDS carve-up of the walk (conv_i8z.inc): digit table, job table, scale / coefficients / bounds, counters, check table,
 # the lane / ring-offset tables, then the rings.  Offsets below kRawBase belong to tables and counters; ring and raw data start there.
 K_TABLES_END = 4 * 3 * 64 * 16 + 256 * 16 + 64 * 4 + 128 + 128 * 4 + 64 * 16 + 2 * 64 * 16   # = 20352 = 0x4f80 (incl. ltab, stab)
+K_MASK_END = K_TABLES_END + 16 * 4      # the row masks; the raw ring starts at K_TABLES_END + 128
 DEFAULT_LAUNCHED = ("Li1ELi2ELi12E",)   # sn_set_option("conv_i8z_variant") default 2: rounds of one x-row, two per ticket, 12 waves
 
 
@@ -86,9 +92,14 @@ def is_ring_access(line):
     if op.startswith(RING_OPS):
         # (the job table, the lane table and the ring-offset table are read with ds_read_b128 / ds_read_b64)
         return not (op in ("ds_read_b128", "ds_read_b64") and in_tables)
-    if op in ("ds_read_b32", "ds_write_b32", "ds_read_b96", "ds_read2_b32"):
+    if op in ("ds_read_b32", "ds_write_b32", "ds_write_b8", "ds_read_b96", "ds_read2_b32"):
         return not in_tables
     return False
+
+
+def is_mask_read(line):
+    off = ds_offset(line)
+    return op_of(line) == "ds_read_b32" and off is not None and K_TABLES_END <= off < K_MASK_END
 
 
 class CFG:
@@ -219,23 +230,37 @@ def audit(name, body, verbose=False):
             errs.append(f"R3: `@zw:wait1` (+{w}) is `{body[wl].strip()}`")
     # ---- R4: folded
     for a in mark["add2"]:
-        for want in ("ds_write_b128", "ds_write_b32"):
+        for want in ("ds_write_b128", "ds_write_b32", "ds_write_b8"):
             why = cfg.walk_back(a, lambda l, want=want: op_of(l) == want,
                                 lambda l: "@zw:" in l and "dma" not in l)
             if why:
                 errs.append(f"R4: `@zw:add2` (+{a}): a path reaches it without the fold pass's {want}: {why}")
     # ---- R5: read
-    rounds_reports = 0
+    rounds_reports = skip_reports = 0
     for a in mark["add3"]:
         behind_mfma = cfg.walk_back(a, lambda l: (op_of(l) or "").startswith("v_mfma"), lambda l: "@zw:spin_exit" in l) is None
         if not behind_mfma:
-            continue      # the report of a ticket without a round: nothing was read
+            # the report of a ticket without a round, of a ticket whose rows lie outside the grid, or of a round with an empty
+            # window: no ring read, but the ticket's row-mask read (every ticket issues it behind the spin exit) must have
+            # returned -- a wait of its own directly above the add
+            why = cfg.walk_back(a, lambda l: "@zw:wait3" in l,
+                                lambda l: (op_of(l) or "").startswith(("ds_read", "v_mfma")) or "@zw:spin_exit" in l)
+            if why:
+                errs.append(f"R5: `@zw:add3` (+{a}, no MFMA): a path reaches it without `@zw:wait3` directly above: {why}")
+            skip_reports += 1
+            continue
         rounds_reports += 1
         why = cfg.walk_back(a, lambda l: "@zw:wait3" in l, lambda l: (op_of(l) or "").startswith(("ds_read", "v_mfma")))
         if why:
             errs.append(f"R5: `@zw:add3` (+{a}): a path reaches it without `@zw:wait3` directly above: {why}")
     if rounds_reports != 1:
         errs.append(f"R5: {rounds_reports} read reports behind MFMAs (expected 1)")
+    if skip_reports < 3:
+        errs.append(f"R5: {skip_reports} read reports without MFMAs (expected the ticket without a round, the ticket outside "
+                    f"the grid and the round with an empty window)")
+    nmask = sum(1 for l in body if is_mask_read(l))
+    if nmask != 1:
+        errs.append(f"R1: {nmask} row-mask reads (expected 1: nine dwords in one ds_read_b32)")
     for w in mark["wait3"]:
         wl = next(k for k in range(w, min(w + 3, n)) if op_of(body[k]) == "s_waitcnt")
         if "lgkmcnt(0)" not in body[wl]:
