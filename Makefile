@@ -24,7 +24,7 @@ FLAGS_tower_score := -ffp-contract=off
 # las.hip: a coordinate is (double)X * scale + offset with the product and the sum rounded once each, as numpy rounds them
 FLAGS_las := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

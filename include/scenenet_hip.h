@@ -1044,6 +1044,61 @@ int sn_las_decode(const void* records, int64_t n, int point_format, int record_l
                   const double offset[3], double* pts, double* classes, int64_t* hist, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K14 -- SemanticKITTI decode: the velodyne and label bytes of B scans -> the pts / labels layout of K1, K9, K10, K12 and
+ *        sn_gather_points, with a per-scan class census.
+ * replaces: core/datasets/semKITTI.py:388-403 -- SemLaserScan.open_scan / open_label per scan on one host core
+ *           (np.fromfile, reshape((-1, 4)), `label & 0xFFFF`, `label >> 16`), the widening to fp64 and an upload per scan.
+ * Provenance: the reference imports SemKITTI_API.auxiliary.laserscan.SemLaserScan (semKITTI.py:26) and does not carry it,
+ *           so nothing here can be pinned against the reference's own output.  The layout is the published SemanticKITTI
+ *           one: .bin is little-endian float32 [n,4] (x, y, z, remission); .label is little-endian uint32 [n] with the
+ *           semantic class in the low 16 bits and the instance id in the high 16.  The oracle is numpy on those definitions.
+ *
+ * scans:       [total,4] f32, the .bin bytes of B scans concatenated, on the device.
+ * label_words: [total] u32, the .label bytes concatenated (nullable: points only).
+ * offsets:     [B+1] i64 CSR on the device: scan b owns the points offsets[b] .. offsets[b+1]-1.  Empty scans are legal
+ *              anywhere, the first and the last included.
+ * pts:         [total,3] f64: the exact widening of x, y, z, by the rule of sn_tiles_unpack's f32 rows -- a NaN keeps its
+ *              sign and payload and gets the quiet bit (f32 bits 0x7f800001 -> f64 bits 0x7ff8000020000000, which is what
+ *              numpy's astype(float64) gives); -0.0 and denormals are carried.
+ * remission:   [total] f32 (nullable): a bit copy of column 3.
+ * labels:      [total] f64 (nullable iff label_words is null).  sem = w & 0xFFFF.  Without lut labels[i] = (double)sem.
+ *              With lut ([n_lut] i32 on the device) labels[i] = (double)lut[sem] when sem < n_lut; otherwise labels[i] =
+ *              -1.0 and unmapped[b] gains one (numpy would raise an IndexError there; the device says so with the counter).
+ * instance:    [total] i32 (nullable; needs label_words): (int32)(w >> 16).
+ * hist:        [B,n_hist] i64 (nullable; needs label_words), ACCUMULATED, not cleared -- the caller zeroes it: hist[b][c]
+ *              gains one for every point of scan b whose output class c satisfies 0 <= c < n_hist.  Negative lut values and
+ *              the -1 of an unmapped word are simply not counted.
+ * bad:         [B] i32 (nullable), WRITTEN: the points of scan b with a non-finite x, y or z (the remission is not looked at).
+ * unmapped:    [B] i32 (nullable; needs lut), WRITTEN: the label words of scan b with sem >= n_lut.
+ * ------------------------------------------------------------------------- */
+
+/* Points per workgroup and pass of the decode kernel (256): host only -- lets a test put its sizes on the seams. */
+int sn_kitti_chunk_points(void);
+
+/* One launch on `stream`, behind one memset node each for bad and unmapped (as sn_tiles_unpack clears bad).  No allocation,
+ * no synchronisation: capturable.  Nothing beyond element total - 1 of any output is written.  The grid is capped at 2048
+ * workgroups; beyond 2048 * 256 points every workgroup takes a run of CONSECUTIVE chunks (not a grid stride), so the scan
+ * its census belongs to changes only where a scan ends.  The census of a workgroup's current scan is summed in LDS and added
+ * with 64-bit (hist) and 32-bit (bad, unmapped) integer atomics, non-zero bins only, when the run enters another scan and
+ * at its end; there are no float atomics and the result does not depend on scheduling.  A chunk that straddles one or
+ * several scan boundaries credits each scan its own points.  The scan of a pass's first point is found from offsets once
+ * per workgroup and pass and stepped from there; it stays inside [0, B) whatever offsets holds.  All index arithmetic is
+ * 64-bit.
+ * Alignment: scans and label_words may sit at any 4-byte alignment; with a 16-byte-aligned scans a point is one 16-byte
+ * load.  The label words are read 16 bytes at a time: the kernel may READ, and never writes, the rest of an aligned 16-byte
+ * granule that holds a valid word (such a granule lies in the same page as a valid byte).  pts and labels are stored 16
+ * bytes at a time wherever the address allows, 8 bytes at either end otherwise.  pts, labels, hist and offsets are 8-byte
+ * aligned, the rest 4-byte; no path issues a byte-wide global access.
+ * SN_ERR_INVALID_ARG, all checked before the launch: null scans, pts or offsets; total <= 0; B <= 0; labels without
+ * label_words or label_words without labels; instance, lut or hist without label_words; n_lut outside 1..65536 with lut;
+ * n_hist outside 1..1024 with hist; unmapped without lut; a misaligned pointer.
+ * SN_ERR_UNSUPPORTED: total > 2^36 or B > 2^20. */
+int sn_kitti_decode(const void* scans, const void* label_words, int64_t total, const int64_t* offsets, int B,
+                    const int32_t* lut, int n_lut, double* pts, double* labels, float* remission, int32_t* instance,
+                    int64_t* hist, int n_hist, int32_t* bad, int32_t* unmapped, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,8 @@ SYMBOLS = {
     "sn_las_chunk_records": (c_int, []),
     "sn_las_decode": (c_int, [_P, ctypes.c_int64, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sn_tower_match": (c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    "sn_kitti_chunk_points": (c_int, []),
+    "sn_kitti_decode": (c_int, [_P, _P, ctypes.c_int64, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -140,6 +142,7 @@ SN_TSCORE_MAX_ROWS, SN_TSCORE_NTOTAL = 1024, 8
 SN_CROP_DISC, SN_CROP_BOX = 0, 1
 SN_CENSUS_MAX_WATCH = 16
 SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
+SN_KITTI_MAX_LUT, SN_KITTI_MAX_HIST = 65536, 1024
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1593,3 +1596,56 @@ def las_decode(records: torch.Tensor, n: int, point_format: int, record_length: 
                               ctypes.cast(sc, c_void_p), ctypes.cast(of, c_void_p), _ptr(pts, torch.float64, "pts"),
                               _ptr(classes, torch.float64, "classes"), _ptr(hist, torch.int64, "hist"), _stream())
     _check(rc, "sn_las_decode")
+
+
+# --------------------------------------------------------------------------- #
+def kitti_chunk_points() -> int:
+    """sn_kitti_chunk_points: points per workgroup and pass of the SemanticKITTI decode kernel (host only)."""
+    return int(load().sn_kitti_chunk_points())
+
+
+def _raw4(t: Optional[torch.Tensor], nbytes: int, name: str) -> Optional[int]:
+    """pointer of a tensor that is taken as raw bytes (uint8, int32 or float32) and holds `nbytes` at least"""
+    if t is None:
+        return None
+    if t.dtype not in (torch.uint8, torch.int32, torch.float32):
+        raise HipLibraryError(f"{name} must be uint8, int32 or float32: the file's bytes as they are (got {t.dtype})")
+    if t.numel() * t.element_size() < nbytes:
+        raise HipLibraryError(f"{name} holds {t.numel() * t.element_size()} bytes, {nbytes} are needed")
+    return _ptr(t, None, name)
+
+
+@_on_tensor_device
+def kitti_decode(scans: torch.Tensor, label_words: Optional[torch.Tensor], total: int, offsets: torch.Tensor,
+                 pts: torch.Tensor, labels: Optional[torch.Tensor] = None, lut: Optional[torch.Tensor] = None,
+                 remission: Optional[torch.Tensor] = None, instance: Optional[torch.Tensor] = None,
+                 hist: Optional[torch.Tensor] = None, bad: Optional[torch.Tensor] = None,
+                 unmapped: Optional[torch.Tensor] = None) -> None:
+    """sn_kitti_decode: scans, the .bin bytes of B scans concatenated (16 * total bytes at any 4-byte address), and
+    label_words, their .label bytes (4 * total; None: points only) -> pts [total,3] f64, labels [total] f64, remission
+    [total] f32, instance [total] i32, hist [B, n_hist] i64 (ACCUMULATED: the caller zeroes it), bad [B] i32 and unmapped
+    [B] i32 (both written), all caller-owned and written in place; offsets [B+1] i64 is the CSR of the scans, lut [n_lut]
+    i32 the optional class remap.  The outputs may be larger: nothing beyond point total - 1 is touched.  One launch, no
+    allocation, no synchronisation."""
+    total = int(total)
+    B = int(offsets.numel()) - 1
+    if total > 0:
+        if pts.numel() < 3 * total or (labels is not None and labels.numel() < total):
+            raise HipLibraryError("pts / labels are smaller than the points they are to hold")
+        if (remission is not None and remission.numel() < total) or (instance is not None and instance.numel() < total):
+            raise HipLibraryError("remission / instance are smaller than the points they are to hold")
+    n_hist = 0
+    if hist is not None:
+        if hist.dim() != 2 or hist.shape[0] != B:
+            raise HipLibraryError(f"hist must be [B, n_hist] with B = {B} (got {tuple(hist.shape)})")
+        n_hist = int(hist.shape[1])
+    for name, t in (("bad", bad), ("unmapped", unmapped)):
+        if t is not None and t.numel() < B:
+            raise HipLibraryError(f"{name} must hold one count per scan")
+    rc = load().sn_kitti_decode(_raw4(scans, 16 * max(total, 0), "scans"), _raw4(label_words, 4 * max(total, 0), "label_words"),
+                                total, _ptr(offsets, torch.int64, "offsets"), B, _ptr(lut, torch.int32, "lut"),
+                                0 if lut is None else int(lut.numel()), _ptr(pts, torch.float64, "pts"),
+                                _ptr(labels, torch.float64, "labels"), _ptr(remission, torch.float32, "remission"),
+                                _ptr(instance, torch.int32, "instance"), _ptr(hist, torch.int64, "hist"), n_hist,
+                                _ptr(bad, torch.int32, "bad"), _ptr(unmapped, torch.int32, "unmapped"), _stream())
+    _check(rc, "sn_kitti_decode")

@@ -139,6 +139,21 @@ __device__ __forceinline__ double dec_f64(unsigned long long u) {
     return __longlong_as_double((long long)u);
 }
 
+// f32 bit pattern -> the f64 bit pattern of the same value, by integer arithmetic only (exact for every finite value and
+// infinity; a NaN keeps its sign and payload and gets the quiet bit, as an IEEE conversion gives), so the result does not
+// depend on the floating-point mode: how K7's f32 rows and K14's velodyne floats are widened.
+__device__ __forceinline__ uint64_t widen_f32_bits(uint32_t u) {
+    const uint64_t sign = (uint64_t)(u >> 31) << 63;
+    const uint32_t e = (u >> 23) & 0xffu, m = u & 0x7fffffu;
+    if (e == 0xffu) return sign | 0x7ff0000000000000ull | ((uint64_t)m << 29) | (m ? 0x0008000000000000ull : 0ull);
+    if (e == 0) {
+        if (m == 0) return sign;
+        const int p = 31 - __clz((int)m);   // m * 2^-149 = 1.f * 2^(p - 149), p in 0..22
+        return sign | ((uint64_t)(p - 149 + 1023) << 52) | ((uint64_t)(m - (1u << p)) << (52 - p));
+    }
+    return sign | ((uint64_t)(e + (1023 - 127)) << 52) | ((uint64_t)m << 29);
+}
+
 // One int of device memory per call (the flag an int8 launch leaves for the gated fp32 launch enqueued behind it, dynamic
 // tile tickets): from a recycled ring for eager launches, from a never-recycled pool while `stream` is capturing
 // (cabi.hip).  nullptr if the pool cannot be allocated.

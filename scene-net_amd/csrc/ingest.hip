@@ -32,18 +32,7 @@ struct alignas(16) U32x4 {
 };
 
 __device__ __forceinline__ uint64_t widen_bits(uint64_t v) { return v; }
-// f32 bit pattern -> the f64 bit pattern of the same value
-__device__ __forceinline__ uint64_t widen_bits(uint32_t u) {
-    const uint64_t sign = (uint64_t)(u >> 31) << 63;
-    const uint32_t e = (u >> 23) & 0xffu, m = u & 0x7fffffu;
-    if (e == 0xffu) return sign | 0x7ff0000000000000ull | ((uint64_t)m << 29) | (m ? 0x0008000000000000ull : 0ull);
-    if (e == 0) {
-        if (m == 0) return sign;
-        const int p = 31 - __clz((int)m);   // m * 2^-149 = 1.f * 2^(p - 149), p in 0..22
-        return sign | ((uint64_t)(p - 149 + 1023) << 52) | ((uint64_t)(m - (1u << p)) << (52 - p));
-    }
-    return sign | ((uint64_t)(e + (1023 - 127)) << 52) | ((uint64_t)m << 29);
-}
+__device__ __forceinline__ uint64_t widen_bits(uint32_t u) { return sn::widen_f32_bits(u); }
 __device__ __forceinline__ bool nonfinite(uint64_t v) { return (v & 0x7ff0000000000000ull) == 0x7ff0000000000000ull; }
 
 // tile of point i: offsets[b] <= i < offsets[b + 1]; stays inside [0, B) whatever offsets holds

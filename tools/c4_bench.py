@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE config 4 on one GPU: SemanticKITTI-like scans (~120k points over 100 m x 100 m x 8 m) -> 128^3 voxel grid ->
 full GENEO bank + convex head -> per-point read-back of the prediction, thresholded (prob_to_label).  Synthetic scans
-(no dataset in the image); scans/s with the scans resident in HBM.  python tools/c4_bench.py [--batch 8]"""
+(no dataset in the image) unless --kitti DIR names a SemanticKITTI root; scans/s with the scans resident in HBM.
+python tools/c4_bench.py [--batch 8] [--kitti DIR]"""
 import argparse
 import os
 import sys
@@ -45,14 +46,22 @@ def main():
     ap.add_argument("--voxel-size", type=float, nargs=3, default=None, metavar=("SX", "SY", "SZ"),
                     help="voxel-size mode (semKITTI.py:453-455): per-scan grid extents computed on the device, grids "
                          "padded to --grid^3 (e.g. 0.8 0.8 0.8 for ~100 m scans at 128^3)")
+    ap.add_argument("--kitti", default=None, metavar="DIR",
+                    help="a SemanticKITTI root (sequences/<seq>/velodyne and labels): its first --batch scans, read through "
+                         "sna.KittiReader, take the place of the synthetic ones")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     specs, names, lambdas, last = synthetic_bank_spec({"cy": 6, "cone": 5, "neg": 5})
     model = sna.SceneNet({"cy": 6, "cone": 5, "neg": 5}, (9, 9, 9))
     apply_bank_spec(model, specs, names, lambdas, last)
     model = model.to(dev)
-    scans, labels = zip(*[kitti_like_scan(s) for s in range(args.batch)])
-    batch = sna.PointBatch.from_tiles(scans, labels, device=dev)
+    if args.kitti is None:
+        scans, labels = zip(*[kitti_like_scan(s) for s in range(args.batch)])
+        batch = sna.PointBatch.from_tiles(scans, labels, device=dev)
+    else:
+        bins, label_files = sna.kitti_scan_lists(args.kitti)
+        batch = sna.KittiReader(dev).read(bins[:args.batch], label_files[:args.batch]).point_batch()
+        args.batch = batch.batch
     # C4 as ONE call: (size-mode | n-mode) grids -> bank conv + head -> per-point read-back (scene-net_amd/pipeline.py)
     pipe = sna.ScenePipeline(model, (args.grid,) * 3, keep_labels=[80.0], voxel_dims=args.voxel_size, per_point=True,
                              tau=0.5)
