@@ -23,8 +23,10 @@ FLAGS_dbscan := -ffp-contract=off
 FLAGS_tower_score := -ffp-contract=off
 # las.hip: a coordinate is (double)X * scale + offset with the product and the sum rounded once each, as numpy rounds them
 FLAGS_las := -ffp-contract=off
+# las_write.hip: an integer coordinate is rint((x - offset) / scale) with the difference and the quotient rounded once each, as numpy rounds them
+FLAGS_las_write := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

@@ -1099,6 +1099,64 @@ int sn_kitti_decode(const void* scans, const void* label_words, int64_t total, c
                     int64_t* hist, int n_hist, int32_t* bad, int32_t* unmapped, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K15 -- LAS encode: the scan layout of K9, K10 and K12 -> the point records of an uncompressed .las file.  K13's mirror.
+ * replaces: what hands a result back in the format it came in.  The reference writes no LAS; with laspy one would copy xyz
+ *           and classes to the host (32 B per point), assign them to the scaled dimensions -- np.rint((x - offset) / scale)
+ *           per column -- and pack the unaligned 20..38-byte records, all on one host core.  Here the records are made on
+ *           the device and go device-to-host as the file will hold them.
+ *
+ * Served:   the point formats 0, 1, 2, 3, 6, 7 and 8.  The waveform formats 4, 5, 9 and 10 are SN_ERR_UNSUPPORTED: there is
+ *           nothing to synthesise a wave packet from.
+ * records:  n records of record_length bytes each, on the device, 16-byte aligned (the writer owns the buffer).
+ *           record_length lies between the format's standard length (20, 28, 26, 34, -, -, 30, 36, 38) and 80; the bytes
+ *           behind the standard length are written as zero.  The field layout is that of the ASPRS LAS 1.4 specification,
+ *           tables 7-15; all fields little-endian.
+ * X, Y, Z:  int32 at bytes 0, 4 and 8.  X = rint(fl(fl(x - ox) / sx)): the subtraction and the division are each rounded
+ *           once and never contracted, the division is a true IEEE fp64 division (never a product with a reciprocal), rint
+ *           rounds half to even -- numpy's np.rint((x - offset) / scale), which is what laspy computes when a scaled
+ *           dimension is assigned.  A NaN quotient writes 0, a quotient below -2^31 INT32_MIN, a quotient above 2^31 - 1
+ *           INT32_MAX (+-inf included); bad[0] then gains one for the POINT, not one per coordinate.
+ * classes:  [n] f64 (nullable: class 0).  c is representable iff c == floor(c) and 0 <= c <= 31 (formats 0..3) or
+ *           0 <= c <= 255 (formats 6..8); otherwise 0 is written and bad[1] gains one.  Formats 0..3: byte 15 = c, the
+ *           synthetic, key-point and withheld bits zero.  Formats 6..8: byte 16 = c and byte 15 = 0.
+ * intensity: [n] u16 (nullable: 0), at byte 12.
+ * byte 14:  "return 1 of 1": 0x09 for the formats 0..3, 0x11 for 6..8.
+ * gps_time: [n] f64 (nullable: 0), a bit copy to byte 20 (formats 1, 3) or byte 22 (formats 6, 7, 8); SN_ERR_INVALID_ARG
+ *           when given for the formats 0 or 2.
+ * rgb:      [n,3] u16 (nullable: 0), at byte 20 (format 2), 28 (format 3) or 30 (formats 7, 8); SN_ERR_INVALID_ARG when
+ *           given for a format without colour.
+ * The NIR field of format 8 and every field not named here (scan angle, user data, point source id, the flag bits) are 0.
+ * box:      [6] i32 (nullable), UPDATED with atomic min / max: min X, max X, min Y, max Y, min Z, max Z of the integers
+ *           written, saturated ones included.  The caller initialises it to INT32_MAX / INT32_MIN pairs.
+ * hist:     [256] i64 (nullable), ACCUMULATED: hist[c] gains the number of records written with class c.
+ * bad:      [2] i64 (nullable), ACCUMULATED: points with a coordinate that did not fit, classes that were not representable.
+ * The caller zeroes hist and bad, so the chunks of one file add up.
+ * ------------------------------------------------------------------------- */
+
+/* Records per workgroup and pass of the encode kernel (256): host only -- lets a test put its sizes on the seams. */
+int sn_las_encode_chunk_records(void);
+
+/* scale, offset: HOST pointers to three doubles each, read during the call only (they travel as kernel arguments: a
+ * captured replay keeps those of capture time).  One launch on `stream`, no allocation, no synchronisation: capturable.
+ * A workgroup builds the byte span of 256 records in LDS and stores it as consecutive 16-byte granules (256 records are a
+ * multiple of 16 bytes and records is 16-byte aligned, so every span starts on a granule); only the tail of the LAST span,
+ * when n * record_length is no multiple of 16, goes out as one 8-, 4-, 2- and 1-byte store each, as its length needs.  No
+ * byte-wide global store in the body of a span.  The kernel writes exactly the bytes [0, n * record_length) of records and
+ * not one byte outside.  The inputs are at their element type's natural alignment only (pts, classes, gps_time 8 bytes,
+ * intensity, rgb 2 bytes) and nothing outside elements 0 .. n - 1 of them is read.  box, hist and bad are reduced per
+ * workgroup on chip and flushed once per workgroup with integer atomics: they do not depend on scheduling.  All byte
+ * arithmetic is 64-bit: n * record_length may exceed 2^31.
+ * SN_ERR_INVALID_ARG: a null pts / records / scale / offset, n <= 0, point_format outside 0..10, record_length below the
+ * format's standard length, a scale that is not finite or is zero, an offset that is not finite, gps_time or rgb for a
+ * format that has no such field, records not 16-byte aligned, pts / classes / gps_time / hist / bad not 8-byte, box not
+ * 4-byte, intensity / rgb not 2-byte aligned;  SN_ERR_UNSUPPORTED: point_format 4, 5, 9 or 10, record_length > 80,
+ * n > 2^36.  All checked before the launch, the SN_ERR_INVALID_ARG ones first. */
+int sn_las_encode(const double* pts, const double* classes, const uint16_t* intensity, const double* gps_time,
+                  const uint16_t* rgb, int64_t n, int point_format, int record_length, const double scale[3],
+                  const double offset[3], void* records, int32_t* box, int64_t* hist, int64_t* bad, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

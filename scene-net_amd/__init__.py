@@ -27,6 +27,7 @@ from .census import (RegionCensus, accept_kinds, crop_accepted, crop_ground_samp
                      region_census, scan_has_class, slab_regions, watch_equal, watch_trunc)
 from .las import (LasHeader, LasReader, LasScan, build_data_samples, las_to_numpy, plan_chunks, read_las, read_las_header,
                   split_slices)
+from .las_write import LasWriter, LasWritten, las_header_bytes, reclassify_las, write_las
 from .kitti import (KittiReader, KittiScans, build_pole_radius_samples, build_pole_samples, kitti_scan_lists, lut_array,
                     read_kitti_scan, semKITTI)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss, GENEO_Loss,
@@ -41,7 +42,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "crop_tower_radius", "crop_two_towers", "crop_tower_samples", "lattice_regions", "merge_to_scan", "PointClusters", "cluster_points", "select_object", "extract_towers",
            "crop_two_towers_samples", "RegionCensus", "region_census", "watch_equal", "watch_trunc", "accept_kinds", "crop_accepted",
            "slab_regions", "crop_ground_samples", "crop_pole_slabs", "pole_radius_samples", "scan_has_class", "LasHeader", "LasReader", "LasScan",
-           "read_las_header", "read_las", "las_to_numpy", "build_data_samples", "plan_chunks", "split_slices", "KittiReader", "KittiScans",
+           "read_las_header", "read_las", "las_to_numpy", "build_data_samples", "plan_chunks", "split_slices", "LasWriter", "LasWritten",
+           "las_header_bytes", "write_las", "reclassify_las", "KittiReader", "KittiScans",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE"]

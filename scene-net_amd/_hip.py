@@ -128,6 +128,8 @@ SYMBOLS = {
     "sn_tower_match": (c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
     "sn_kitti_chunk_points": (c_int, []),
     "sn_kitti_decode": (c_int, [_P, _P, ctypes.c_int64, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "sn_las_encode_chunk_records": (c_int, []),
+    "sn_las_encode": (c_int, [_P, _P, _P, _P, _P, ctypes.c_int64, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -1596,6 +1598,58 @@ def las_decode(records: torch.Tensor, n: int, point_format: int, record_length: 
                               ctypes.cast(sc, c_void_p), ctypes.cast(of, c_void_p), _ptr(pts, torch.float64, "pts"),
                               _ptr(classes, torch.float64, "classes"), _ptr(hist, torch.int64, "hist"), _stream())
     _check(rc, "sn_las_decode")
+
+
+# --------------------------------------------------------------------------- #
+def las_encode_chunk_records() -> int:
+    """sn_las_encode_chunk_records: records per workgroup and pass of the LAS encode kernel (host only)."""
+    return int(load().sn_las_encode_chunk_records())
+
+
+def _u16_ptr(t: Optional[torch.Tensor], name: str) -> Optional[int]:
+    """pointer of a tensor of 16-bit words: uint16, or int16 taken as the same bits"""
+    if t is not None and t.dtype == torch.int16:
+        return _ptr(t, torch.int16, name)
+    return _ptr(t, torch.uint16, name)
+
+
+@_on_tensor_device
+def las_encode(pts: torch.Tensor, n: int, point_format: int, record_length: int, scale: Sequence[float],
+               offset: Sequence[float], records: torch.Tensor, classes: Optional[torch.Tensor] = None,
+               intensity: Optional[torch.Tensor] = None, gps_time: Optional[torch.Tensor] = None,
+               rgb: Optional[torch.Tensor] = None, box: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+               bad: Optional[torch.Tensor] = None) -> None:
+    """sn_las_encode: pts [n,3] f64, classes [n] f64 | None, intensity [n] u16 | None, gps_time [n] f64 | None, rgb [n,3] u16
+    | None -> n records of record_length bytes at the start of `records`, a 16-byte aligned uint8 tensor; box [6] i32 | None
+    (UPDATED by min / max: the caller sets INT32_MAX / INT32_MIN pairs), hist [256] i64 | None and bad [2] i64 | None
+    (ACCUMULATED: the caller zeroes them).  The inputs may be larger than n; nothing beyond byte n * record_length - 1 of
+    records is touched.  One launch, no allocation, no synchronisation."""
+    n, record_length = int(n), int(record_length)
+    if records.dtype != torch.uint8 or records.dim() != 1:
+        raise HipLibraryError("records must be a one-dimensional uint8 tensor (the file's bytes as they will be)")
+    if n > 0 and records.numel() < n * record_length:
+        raise HipLibraryError(f"records holds {records.numel()} bytes, {n} records of {record_length} need more")
+    for name, t, per in (("pts", pts, 3), ("classes", classes, 1), ("intensity", intensity, 1), ("gps_time", gps_time, 1),
+                         ("rgb", rgb, 3)):
+        if t is not None and n > 0 and t.numel() < per * n:
+            raise HipLibraryError(f"{name} holds {t.numel()} elements, {n} points need {per * n}")
+    if box is not None and box.numel() != 6:
+        raise HipLibraryError("box must hold 6 integers")
+    if hist is not None and hist.numel() != 256:
+        raise HipLibraryError("hist must hold 256 counts")
+    if bad is not None and bad.numel() != 2:
+        raise HipLibraryError("bad must hold 2 counts")
+    if len(scale) != 3 or len(offset) != 3:
+        raise HipLibraryError("scale and offset have 3 entries each")
+    sc = (ctypes.c_double * 3)(*[float(v) for v in scale])
+    of = (ctypes.c_double * 3)(*[float(v) for v in offset])
+    rc = load().sn_las_encode(_ptr(pts, torch.float64, "pts"), _ptr(classes, torch.float64, "classes"),
+                              _u16_ptr(intensity, "intensity"), _ptr(gps_time, torch.float64, "gps_time"),
+                              _u16_ptr(rgb, "rgb"), n, int(point_format), record_length, ctypes.cast(sc, c_void_p),
+                              ctypes.cast(of, c_void_p), _ptr(records, torch.uint8, "records"),
+                              _ptr(box, torch.int32, "box"), _ptr(hist, torch.int64, "hist"), _ptr(bad, torch.int64, "bad"),
+                              _stream())
+    _check(rc, "sn_las_encode")
 
 
 # --------------------------------------------------------------------------- #
