@@ -25,8 +25,10 @@ FLAGS_tower_score := -ffp-contract=off
 FLAGS_las := -ffp-contract=off
 # las_write.hip: an integer coordinate is rint((x - offset) / scale) with the difference and the quotient rounded once each, as numpy rounds them
 FLAGS_las_write := -ffp-contract=off
+# voxel_cloud.hip: a colour is (1 + c) * 255.0 with the sum and the product rounded once each, as numpy rounds them
+FLAGS_voxel_cloud := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

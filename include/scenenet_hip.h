@@ -1157,6 +1157,67 @@ int sn_las_encode(const double* pts, const double* classes, const uint16_t* inte
                   const double offset[3], void* records, int32_t* box, int64_t* hist, int64_t* bad, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K16 -- coloured voxel clouds: the non-zero voxels of B grids as rows (x, y, z, r, g, b), a CSR batch of B clouds.
+ * replaces: the data half of plot_voxelgrid (utils/voxelization.py:45-144) and the color_pointcloud behind it
+ *           (utils/pcd_processing.py:525-574): a Python loop over grid.nonzero() and an np.where per voxel on the host, after
+ *           a .detach().cpu().numpy() of each logged grid (core/lit_modules/lit_model_wrappers.py:222-233).
+ *
+ * grid:     [B, n0, n1, n2] = [B, Z, X, Y] of `dtype` (SN_F32 | SN_F64 | SN_U8 | SN_OCC8), element-aligned.  A value is read
+ *           as fp64 (an f32 widens exactly).
+ * rows:     cloud b holds one row per LIVE cell of tile b, in C order of (z, x, y) -- grid.nonzero() order.  The row is
+ *           (x, y, z, 255 r, 255 g, 255 b), all fp64.
+ *   SN_CLOUD_DENSITY  live iff value != 0 (-0.0 is zero, NaN is not).  c < 0: (r, g, b) = (1 + c, 1 + c, 1), otherwise
+ *                     (1, 1 - c, 1 - c); each sum is rounded once, then multiplied by 255.0 and rounded once, never
+ *                     contracted.  A NaN cell is written as (255, NaN, NaN) and counted in bad[b][0] (the reference raises
+ *                     IndexError on one).  bad[b][1] counts the live cells that are not NaN and whose colour has a channel
+ *                     below 0 or above 255 (|c| > 1).
+ *   SN_CLOUD_RANGES   lin = numpy.linspace(0, 1, r) and step = (1 / r) / 2, both formed on the host as numpy forms them.
+ *                     Live iff value > lin[1] (NaN, negatives and zero drop out).  The colour is row
+ *                     argmin_j |(value - lin[j]) - step| of the table (differences in fp64 in exactly this order, the first
+ *                     minimum wins), times 255.0.  The table [r,3] f64 is the caller's (the reference: cm.jet(lin)[:, :3]
+ *                     with row 0 forced to (1, 1, 1)).  r is in 2..32 and not read in the density mode.  bad[b] = (0, 0).
+ * desc:     null: x, y, z are the cell's indices (i1, i2, i0) as doubles -- the reference's form.  Given: desc
+ *           [B, SN_DESC_LEN(n1, n2, n0)] is the voxelisation's descriptor and x, y, z are the voxel centres
+ *           (e[k] + e[k+1]) * 0.5 from the tile's own edge tables, the sum and the product rounded once each; a cell whose
+ *           upper edge on any axis is not finite (a size-mode padding cell) is not live, whatever it holds -- the rule of
+ *           sn_gather_points.  (Build-defined: the reference has no such form.)
+ * rgb16:    [capacity,3] u16 for the LAS writer (K15), build-defined: clamp(rint(v), 0, 255) * 257 of the row's 255 r,
+ *           255 g, 255 b; NaN gives 0.
+ * ------------------------------------------------------------------------- */
+#define SN_CLOUD_DENSITY 0
+#define SN_CLOUD_RANGES 1
+
+/* Cells per workgroup (1024): host only -- lets a test put its sizes on the seams. */
+int sn_voxel_cloud_chunk_cells(void);
+/* Workspace bytes of sn_voxel_cloud_count / _scatter for B tiles of V = n0 * n1 * n2 cells: 8 * B * (3 * chunks + 1),
+ * chunks = ceil(V / sn_voxel_cloud_chunk_cells()).  0 for a shape the entries refuse (B <= 0, V <= 0, B > 65535, V >= 2^31). */
+size_t sn_voxel_cloud_ws_bytes(int B, int64_t V);
+
+/* Live-cell counts of every (tile, workgroup) into ws, their exclusive prefixes per tile in place, the CSR offsets [B+1]
+ * (the TRUE sizes) and bad [B,2] i64, reduced from per-workgroup slots in a fixed order.  Three launches on `stream`
+ * (count, prefix, offsets); every slot is written by exactly one workgroup: no memset, no atomics, no workgroup waits for
+ * another.  No allocation, no synchronisation: capturable; results do not depend on scheduling.
+ * SN_ERR_INVALID_ARG: a null grid / ws / offsets / bad, B or an extent <= 0, an unknown mode or dtype, r outside 2..32 in
+ * the ranges mode, ws_bytes < sn_voxel_cloud_ws_bytes, a misaligned pointer (grid: its element; the others 8 bytes);
+ * SN_ERR_UNSUPPORTED: B > 65535 or n0 * n1 * n2 >= 2^31.  All checked before any launch. */
+int sn_voxel_cloud_count(const void* grid, int dtype, int B, int n0, int n1, int n2, int mode, int r, const double* desc,
+                         void* ws, size_t ws_bytes, int64_t* offsets, int64_t* bad, sn_stream_t stream);
+
+/* Called with the same grid / mode / r / desc and the ws / offsets that sn_voxel_cloud_count left: writes output row
+ * offsets[b] + rank of every live cell whose output index is < capacity into rows [capacity,6] f64 (nullable, 16-byte
+ * aligned), xyz [capacity,3] f64 (nullable) and rgb16 [capacity,3] u16 (nullable); one of rows and xyz is given.  Rows at
+ * or beyond capacity and everything beyond offsets[B] are NOT touched.  table_host: [r,3] f64 on the HOST, read during
+ * the call only (it travels in the launch's arguments: a captured replay keeps the one of capture time); null in the
+ * density mode.  One launch; no allocation, no synchronisation: capturable.  Vector stores only.
+ * SN_ERR_INVALID_ARG: as sn_voxel_cloud_count (bad aside), and a null table_host in the ranges mode, neither rows nor xyz,
+ * capacity < 0, rows not 16-byte, xyz not 8-byte, rgb16 not 2-byte aligned;  SN_ERR_UNSUPPORTED: as sn_voxel_cloud_count. */
+int sn_voxel_cloud_scatter(const void* grid, int dtype, int B, int n0, int n1, int n2, int mode, int r,
+                           const double* table_host, const double* desc, const void* ws, size_t ws_bytes,
+                           const int64_t* offsets, int64_t capacity, double* rows, double* xyz, uint16_t* rgb16,
+                           sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

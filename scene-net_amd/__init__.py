@@ -30,6 +30,8 @@ from .las import (LasHeader, LasReader, LasScan, build_data_samples, las_to_nump
 from .las_write import LasWriter, LasWritten, las_header_bytes, reclassify_las, write_las
 from .kitti import (KittiReader, KittiScans, build_pole_radius_samples, build_pole_samples, kitti_scan_lists, lut_array,
                     read_kitti_scan, semKITTI)
+from .voxel_cloud import (VoxelCloud, jet_ranges, plot_quantile_uncertainty, plot_voxelgrid, voxel_cloud,
+                          write_voxel_cloud_las)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss, GENEO_Loss,
                          GENEO_Tversky_Loss, TverskyLoss, WeightedMSE)
 
@@ -44,6 +46,7 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "slab_regions", "crop_ground_samples", "crop_pole_slabs", "pole_radius_samples", "scan_has_class", "LasHeader", "LasReader", "LasScan",
            "read_las_header", "read_las", "las_to_numpy", "build_data_samples", "plan_chunks", "split_slices", "LasWriter", "LasWritten",
            "las_header_bytes", "write_las", "reclassify_las", "KittiReader", "KittiScans",
+           "VoxelCloud", "voxel_cloud", "plot_voxelgrid", "plot_quantile_uncertainty", "jet_ranges", "write_voxel_cloud_las",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE"]

@@ -130,6 +130,11 @@ SYMBOLS = {
     "sn_kitti_decode": (c_int, [_P, _P, ctypes.c_int64, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "sn_las_encode_chunk_records": (c_int, []),
     "sn_las_encode": (c_int, [_P, _P, _P, _P, _P, ctypes.c_int64, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "sn_voxel_cloud_chunk_cells": (c_int, []),
+    "sn_voxel_cloud_ws_bytes": (ctypes.c_size_t, [_I, ctypes.c_int64]),
+    "sn_voxel_cloud_count": (c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_size_t, _P, _P, _P]),
+    "sn_voxel_cloud_scatter": (c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P,
+                                       _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -145,6 +150,7 @@ SN_CROP_DISC, SN_CROP_BOX = 0, 1
 SN_CENSUS_MAX_WATCH = 16
 SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
 SN_KITTI_MAX_LUT, SN_KITTI_MAX_HIST = 65536, 1024
+SN_CLOUD_DENSITY, SN_CLOUD_RANGES, SN_CLOUD_MAX_R = 0, 1, 32
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1703,3 +1709,79 @@ def kitti_decode(scans: torch.Tensor, label_words: Optional[torch.Tensor], total
                                 _ptr(instance, torch.int32, "instance"), _ptr(hist, torch.int64, "hist"), n_hist,
                                 _ptr(bad, torch.int32, "bad"), _ptr(unmapped, torch.int32, "unmapped"), _stream())
     _check(rc, "sn_kitti_decode")
+
+
+# --------------------------------------------------------------------------- #
+def voxel_cloud_chunk_cells() -> int:
+    """sn_voxel_cloud_chunk_cells: cells per workgroup of the voxel-cloud kernels (host only)."""
+    return int(load().sn_voxel_cloud_chunk_cells())
+
+
+def voxel_cloud_ws_bytes(B: int, V: int) -> int:
+    """sn_voxel_cloud_ws_bytes: scratch bytes of voxel_cloud_count / voxel_cloud_scatter over B tiles of V cells (host only)."""
+    need = int(load().sn_voxel_cloud_ws_bytes(int(B), int(V)))
+    if need == 0:
+        raise HipLibraryError(f"sn_voxel_cloud_count serves no batch of {B} grids with {V} cells each (1 <= B <= 65535, "
+                              "1 <= cells < 2^31)")
+    return need
+
+
+def _cloud_head(grids, desc):
+    if grids.dim() != 4 or grids.dtype not in _DT or grids.dtype == torch.bfloat16:
+        raise HipLibraryError("grids must be [B,n0,n1,n2] float32/float64/uint8/bool")
+    B, n0, n1, n2 = (int(v) for v in grids.shape)
+    if desc is not None and tuple(desc.shape) != (B, desc_len(n1, n2, n0)):
+        raise HipLibraryError(f"desc must be [B, desc_len(nx, ny, nz)] = [{B}, {desc_len(n1, n2, n0)}] "
+                              f"(got {tuple(desc.shape)})")
+    return B, n0, n1, n2
+
+
+@_on_tensor_device
+def voxel_cloud_count(grids: torch.Tensor, mode: int, r: int, desc: Optional[torch.Tensor], ws: torch.Tensor,
+                      offsets: torch.Tensor, bad: torch.Tensor) -> None:
+    """sn_voxel_cloud_count: grids [B,n0,n1,n2] -> offsets [B+1] i64, bad [B,2] i64 and the per-workgroup prefixes in `ws`
+    (voxel_cloud_ws_bytes), all caller-owned.  Three launches, no allocation, no synchronisation."""
+    B, n0, n1, n2 = _cloud_head(grids, desc)
+    if offsets.numel() != B + 1 or bad.numel() != 2 * B:
+        raise HipLibraryError("offsets must hold B + 1 entries and bad 2 * B")
+    rc = load().sn_voxel_cloud_count(_ptr(grids, None, "grids"), _DT[grids.dtype], B, n0, n1, n2, int(mode), int(r),
+                                     _ptr(desc, torch.float64, "desc"), _ptr(ws, None, "ws"),
+                                     ws.numel() * ws.element_size(), _ptr(offsets, torch.int64, "offsets"),
+                                     _ptr(bad, torch.int64, "bad"), _stream())
+    _check(rc, "sn_voxel_cloud_count")
+
+
+@_on_tensor_device
+def voxel_cloud_scatter(grids: torch.Tensor, mode: int, r: int, table, desc: Optional[torch.Tensor], ws: torch.Tensor,
+                        offsets: torch.Tensor, rows: Optional[torch.Tensor], xyz: Optional[torch.Tensor] = None,
+                        rgb16: Optional[torch.Tensor] = None, capacity: Optional[int] = None) -> None:
+    """sn_voxel_cloud_scatter behind voxel_cloud_count on the same arguments: fills rows [cap,6] f64 and / or xyz [cap,3] f64
+    and rgb16 [cap,3] (u)int16; `table`: [r,3] doubles on the host (None in the density mode).  Rows at or beyond the
+    capacity -- the outputs' row count, or a smaller `capacity` -- and beyond offsets[B] are left as they are.  One launch,
+    no allocation, no synchronisation."""
+    B, n0, n1, n2 = _cloud_head(grids, desc)
+    have = [t for t in (rows, xyz, rgb16) if t is not None]
+    if rows is None and xyz is None:
+        raise HipLibraryError("one of rows and xyz must be given")
+    for t, cols, name in ((rows, 6, "rows"), (xyz, 3, "xyz"), (rgb16, 3, "rgb16")):
+        if t is not None and (t.dim() != 2 or t.shape[1] != cols):
+            raise HipLibraryError(f"{name} must be [capacity, {cols}] (got {tuple(t.shape)})")
+    least = min(int(t.shape[0]) for t in have)
+    capacity = least if capacity is None else int(capacity)
+    if capacity > least:
+        raise HipLibraryError("capacity exceeds the rows of an output")
+    if rgb16 is not None and rgb16.dtype not in (torch.uint16, torch.int16):
+        raise HipLibraryError(f"rgb16 must be uint16 (got {rgb16.dtype})")
+    t_keep, t_ptr = None, None
+    if table is not None:
+        flat = [float(v) for row in table for v in row]
+        if len(flat) != 3 * int(r):
+            raise HipLibraryError(f"the colour table must be [r, 3] = [{int(r)}, 3]")
+        t_keep = (ctypes.c_double * len(flat))(*flat)
+        t_ptr = ctypes.cast(t_keep, c_void_p)
+    rc = load().sn_voxel_cloud_scatter(_ptr(grids, None, "grids"), _DT[grids.dtype], B, n0, n1, n2, int(mode), int(r), t_ptr,
+                                       _ptr(desc, torch.float64, "desc"), _ptr(ws, None, "ws"),
+                                       ws.numel() * ws.element_size(), _ptr(offsets, torch.int64, "offsets"), capacity,
+                                       _ptr(rows, torch.float64, "rows"), _ptr(xyz, torch.float64, "xyz"),
+                                       _ptr(rgb16, None, "rgb16"), _stream())
+    _check(rc, "sn_voxel_cloud_scatter")
