@@ -27,13 +27,15 @@ FLAGS_las := -ffp-contract=off
 FLAGS_las_write := -ffp-contract=off
 # voxel_cloud.hip: a colour is (1 + c) * 255.0 with the sum and the product rounded once each, as numpy rounds them
 FLAGS_voxel_cloud := -ffp-contract=off
+# thin.hip: bins with K1's fp64 rounding sequence (binning.h) and forms its uniform without a contracted multiply-add
+FLAGS_thin := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so
 
-$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h
+$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h $(SRC)/binning.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(CXXFLAGS) $(FLAGS_$*) -c $< -o $@
 

@@ -1218,6 +1218,78 @@ int sn_voxel_cloud_scatter(const void* grid, int dtype, int B, int n0, int n1, i
                            sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K17 -- thinning: the rows of a CSR batch kept with a probability per tile and group, compacted in scan order.
+ * replaces: the two downsamplers of utils/pcd_processing.py -- downsampling (:375-420) and downsampling_relative_height
+ *           (:423-474): a Python loop over the points into a dict of lists keyed by voxel_n / voxel_z, then per group
+ *           np.random.rand(len(group)) and group[selected <= threshold].
+ *
+ * batch:    pts [total,3] f64, labels [total] f64 or null, offsets [B+1] i64 -- the ragged CSR layout of K1, with
+ *           offsets[0] = 0 and offsets[B] = total (a row that no tile owns is not kept).  Empty tiles are legal.
+ * rule:     row j of tile b (j counted from offsets[b]) is kept iff it is binned and u <= thr[b][g], the comparison
+ *           taken literally in fp64: a NaN on either side keeps nothing.  thr [B, G] f64 is the caller's, on the DEVICE.
+ *   SN_THIN_GROUP_NONE   g = 0, G = 1.  No descriptor is read (desc, nx, ny, nz are ignored) and every row is binned.
+ *   SN_THIN_GROUP_Z      g = the row's z index, G = nz
+ *   SN_THIN_GROUP_VOXEL  g = the row's flat [z][x][y] index (iz * nx + ix) * ny + iy, G = nx * ny * nz
+ *           The binning is K1's, bit for bit (the same device function as sn_voxel_scatter, the rule stated there), with
+ *           desc [B, SN_DESC_LEN(nx, ny, nz)] as sn_voxel_prepare and its siblings build it.  A row with a NaN
+ *           coordinate or outside the table on ANY axis is not binned: it is not kept and is counted in unbinned [B].
+ *           A size-mode descriptor is accepted with the caveat of sn_voxel_desc_sized: the padded table is used as it
+ *           stands, so a foreign row above a tile's own last edge lands in the padding cell n_a, takes that cell's
+ *           threshold and is NOT counted in unbinned.
+ * uniform:  exactly one of u and seed is given (both on the device).
+ *   u     [total] f64, indexed like pts.
+ *   seed  [1] u64, READ BY THE KERNEL: a captured graph is re-seeded by a one-element copy.  Row j of tile b draws
+ *         Philox4x32-10 (10 rounds, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with
+ *         key (seed lo, seed hi) and counter (j lo, j hi, t lo, t hi), t = tile_ids[b] (i64 [B], nullable: t = b), and
+ *         u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53 of output words 0 and 1: numpy's 53-bit double, in [0, 1).
+ *         A tile's rows depend on its seed, id, points and descriptor alone -- not on its place in a batch.
+ * output:   the batch's kept rows in scan order (a stable compaction of the packed array, hence of every tile), as 64-bit
+ *           patterns (NaN payloads and -0.0 unchanged, as K7 and K9).  offsets_out [B+1] i64: offsets_out[b] = rows kept
+ *           in front of packed index offsets[b] -- the thinned batch's CSR offsets, TRUE sizes whatever the capacity.
+ *           first [B, G] u64 (nullable): per group the smallest in-tile index j of any BINNED row, kept or not; all ones
+ *           for a group no row falls in.  (What orders the groups as the reference's dict does.)
+ * ------------------------------------------------------------------------- */
+#define SN_THIN_GROUP_NONE 0
+#define SN_THIN_GROUP_Z 1
+#define SN_THIN_GROUP_VOXEL 2
+
+/* Workspace bytes of sn_thin_count / sn_thin_scatter: 8 * (2 * (chunks + 1) + 32 * chunks), chunks = ceil(total /
+ * sn_thin_chunk_points()) -- two prefix rows and two bits per row of the batch.  0 for a shape the entries refuse
+ * (total <= 0, B <= 0, total > 2^33, B > 65536). */
+size_t sn_thin_ws_bytes(int64_t total, int B);
+/* Rows per workgroup (1024): host only -- lets a test put its sizes on the seams. */
+int sn_thin_chunk_points(void);
+
+/* The decision of every row as one bit in ws, the kept and the unbinned counts of every workgroup and their exclusive
+ * prefixes, offsets_out [B+1] and unbinned [B].  Three launches on `stream` (count, prefix, offsets), in front of them one
+ * memset node over `first` when it is given; `first` is then reduced by 64-bit integer atomic min (an integer minimum:
+ * independent of scheduling), the only atomics.  Every slot of ws is written by exactly one workgroup.  No allocation,
+ * no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null pts / offsets / thr / ws / offsets_out / unbinned, total <= 0, B <= 0, an unknown group, both
+ * or neither of u and seed, a group other than SN_THIN_GROUP_NONE with a null desc or an extent <= 0, ws_bytes <
+ * sn_thin_ws_bytes(total, B), a pointer that is not 8-byte aligned;  SN_ERR_UNSUPPORTED: total > 2^33, B > 65536,
+ * edge tables (nx + ny + nz + 3 doubles, and nz more with SN_THIN_GROUP_Z) beyond 64 KiB of LDS, nx * ny * nz >= 2^31.
+ * All checked before any launch. */
+int sn_thin_count(const double* pts, const int64_t* offsets, int64_t total, int B, int group, const double* desc, int nx,
+                  int ny, int nz, const double* thr, const double* u, const uint64_t* seed, const int64_t* tile_ids, void* ws,
+                  size_t ws_bytes, int64_t* offsets_out, int64_t* unbinned, uint64_t* first, sn_stream_t stream);
+
+/* Called with the same batch and rule and the ws that sn_thin_count left: writes the kept row of global rank o (tile b's
+ * rows start at offsets_out[b]) for every o < capacity -- out_pts [capacity,3], out_labels [capacity] (null iff labels is
+ * null), out_src [capacity] i64 (nullable: the row's index in the packed input), out_key [capacity] i32 (nullable: the
+ * row's group g).  Rows at or beyond capacity and everything beyond offsets_out[B] are NOT touched.  The decision is read
+ * from ws (one bit per row); it is made again -- same function, same bits -- when out_key is wanted with a grouped rule,
+ * to find the groups.  One launch; no allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: as sn_thin_count (offsets_out, unbinned, first aside), and a null out_pts, capacity < 0, out_labels
+ * without labels or the reverse, labels / out_pts / out_labels / out_src not 8-byte or out_key not 4-byte aligned;
+ * SN_ERR_UNSUPPORTED: as sn_thin_count. */
+int sn_thin_scatter(const double* pts, const double* labels, const int64_t* offsets, int64_t total, int B, int group,
+                    const double* desc, int nx, int ny, int nz, const double* thr, const double* u, const uint64_t* seed,
+                    const int64_t* tile_ids, const void* ws, size_t ws_bytes, int64_t capacity, double* out_pts,
+                    double* out_labels, int64_t* out_src, int32_t* out_key, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ from .kitti import (KittiReader, KittiScans, build_pole_radius_samples, build_po
                     read_kitti_scan, semKITTI)
 from .voxel_cloud import (VoxelCloud, jet_ranges, plot_quantile_uncertainty, plot_voxelgrid, voxel_cloud,
                           write_voxel_cloud_las)
+from .thin import (ThinnedPoints, ThinPoints, downsampling, downsampling_relative_height, height_thresholds,
+                   philox_uniforms, thin_points, uniform_thresholds)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss, GENEO_Loss,
                          GENEO_Tversky_Loss, TverskyLoss, WeightedMSE)
 
@@ -47,6 +49,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "read_las_header", "read_las", "las_to_numpy", "build_data_samples", "plan_chunks", "split_slices", "LasWriter", "LasWritten",
            "las_header_bytes", "write_las", "reclassify_las", "KittiReader", "KittiScans",
            "VoxelCloud", "voxel_cloud", "plot_voxelgrid", "plot_quantile_uncertainty", "jet_ranges", "write_voxel_cloud_las",
+           "ThinnedPoints", "ThinPoints", "thin_points", "downsampling", "downsampling_relative_height", "height_thresholds",
+           "uniform_thresholds", "philox_uniforms",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE"]

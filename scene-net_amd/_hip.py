@@ -135,6 +135,12 @@ SYMBOLS = {
     "sn_voxel_cloud_count": (c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_size_t, _P, _P, _P]),
     "sn_voxel_cloud_scatter": (c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P,
                                        _P, _P]),
+    "sn_thin_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I]),
+    "sn_thin_chunk_points": (c_int, []),
+    "sn_thin_count": (c_int, [_P, _P, ctypes.c_int64, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P,
+                              _P]),
+    "sn_thin_scatter": (c_int, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t,
+                                ctypes.c_int64, _P, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -151,6 +157,7 @@ SN_CENSUS_MAX_WATCH = 16
 SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
 SN_KITTI_MAX_LUT, SN_KITTI_MAX_HIST = 65536, 1024
 SN_CLOUD_DENSITY, SN_CLOUD_RANGES, SN_CLOUD_MAX_R = 0, 1, 32
+SN_THIN_GROUP_NONE, SN_THIN_GROUP_Z, SN_THIN_GROUP_VOXEL = 0, 1, 2
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1785,3 +1792,92 @@ def voxel_cloud_scatter(grids: torch.Tensor, mode: int, r: int, table, desc: Opt
                                        _ptr(rows, torch.float64, "rows"), _ptr(xyz, torch.float64, "xyz"),
                                        _ptr(rgb16, None, "rgb16"), _stream())
     _check(rc, "sn_voxel_cloud_scatter")
+
+
+# --------------------------------------------------------------------------- #
+def thin_chunk_points() -> int:
+    """sn_thin_chunk_points: rows per workgroup of the thinning kernels (host only)."""
+    return int(load().sn_thin_chunk_points())
+
+
+def thin_ws_bytes(total: int, B: int) -> int:
+    """sn_thin_ws_bytes: scratch bytes of thin_count / thin_scatter over a batch of `total` rows in B tiles (host only)."""
+    need = int(load().sn_thin_ws_bytes(int(total), int(B)))
+    if need == 0:
+        raise HipLibraryError(f"sn_thin_count serves no batch of {total} rows in {B} tiles (1 <= total <= 2^33, "
+                              "1 <= B <= 65536)")
+    return need
+
+
+def thin_groups(group: int, n_xyz: Sequence[int]) -> int:
+    """G of a rule: thresholds per tile (1, nz or nx * ny * nz)."""
+    nx, ny, nz = (int(v) for v in n_xyz)
+    return {SN_THIN_GROUP_NONE: 1, SN_THIN_GROUP_Z: nz, SN_THIN_GROUP_VOXEL: nx * ny * nz}[int(group)]
+
+
+def _thin_head(pts, offsets, group, desc, n_xyz, thr, u, seed, tile_ids):
+    """The checks and the leading arguments sn_thin_count and sn_thin_scatter share."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [total, 3] (got {tuple(pts.shape)})")
+    total, B = int(pts.shape[0]), int(offsets.numel()) - 1
+    nx, ny, nz = (int(v) for v in n_xyz)
+    G = thin_groups(group, (nx, ny, nz))
+    if thr.numel() != B * G:
+        raise HipLibraryError(f"thr must be [B, G] = [{B}, {G}] (got {tuple(thr.shape)})")
+    if int(group) != SN_THIN_GROUP_NONE and (desc is None or tuple(desc.shape) != (B, desc_len(nx, ny, nz))):
+        raise HipLibraryError(f"desc must be [B, desc_len(nx, ny, nz)] = [{B}, {desc_len(nx, ny, nz)}]")
+    if u is not None and u.numel() != total:
+        raise HipLibraryError("u must hold one entry per row of pts")
+    if seed is not None and seed.numel() != 1:
+        raise HipLibraryError("seed must hold one 64-bit word")
+    if tile_ids is not None and tile_ids.numel() != B:
+        raise HipLibraryError("tile_ids must hold one entry per tile")
+    return total, B, G, (_ptr(offsets, torch.int64, "offsets"), total, B, int(group), _ptr(desc, torch.float64, "desc"),
+                         nx, ny, nz, _ptr(thr, torch.float64, "thr"), _ptr(u, torch.float64, "u"),
+                         _ptr(seed, torch.int64, "seed"), _ptr(tile_ids, torch.int64, "tile_ids"))
+
+
+@_on_tensor_device
+def thin_count(pts: torch.Tensor, offsets: torch.Tensor, group: int, desc: Optional[torch.Tensor], n_xyz: Sequence[int],
+               thr: torch.Tensor, u: Optional[torch.Tensor], seed: Optional[torch.Tensor], tile_ids: Optional[torch.Tensor],
+               ws: torch.Tensor, offsets_out: torch.Tensor, unbinned: torch.Tensor,
+               first: Optional[torch.Tensor] = None) -> None:
+    """sn_thin_count: pts [total,3] f64, offsets [B+1] i64, thr [B,G] f64, u [total] f64 or seed [1] i64 (the u64's bits),
+    tile_ids [B] i64 | None -> offsets_out [B+1] i64, unbinned [B] i64, first [B,G] i64 | None (all ones = -1: an empty
+    group) and the decisions in `ws` (thin_ws_bytes), all caller-owned.  No allocation, no synchronisation."""
+    total, B, G, head = _thin_head(pts, offsets, group, desc, n_xyz, thr, u, seed, tile_ids)
+    if offsets_out.numel() != B + 1 or unbinned.numel() != B:
+        raise HipLibraryError("offsets_out must hold B + 1 entries and unbinned B")
+    if first is not None and first.numel() != B * G:
+        raise HipLibraryError(f"first must be [B, G] = [{B}, {G}]")
+    rc = load().sn_thin_count(_ptr(pts, torch.float64, "pts"), *head, _ptr(ws, None, "ws"), ws.numel() * ws.element_size(),
+                              _ptr(offsets_out, torch.int64, "offsets_out"), _ptr(unbinned, torch.int64, "unbinned"),
+                              _ptr(first, torch.int64, "first"), _stream())
+    _check(rc, "sn_thin_count")
+
+
+@_on_tensor_device
+def thin_scatter(pts: torch.Tensor, labels: Optional[torch.Tensor], offsets: torch.Tensor, group: int,
+                 desc: Optional[torch.Tensor], n_xyz: Sequence[int], thr: torch.Tensor, u: Optional[torch.Tensor],
+                 seed: Optional[torch.Tensor], tile_ids: Optional[torch.Tensor], ws: torch.Tensor, out_pts: torch.Tensor,
+                 out_labels: Optional[torch.Tensor], out_src: Optional[torch.Tensor], out_key: Optional[torch.Tensor] = None,
+                 capacity: Optional[int] = None) -> None:
+    """sn_thin_scatter behind thin_count on the same arguments: fills out_pts [rows,3] f64, out_labels [rows] f64 (iff
+    labels), out_src [rows] i64 and out_key [rows] i32 (both optional); rows at or beyond the capacity -- out_pts' row
+    count, or a smaller `capacity` -- and beyond offsets_out[B] are left as they are.  One launch, no allocation, no
+    synchronisation."""
+    total, B, G, head = _thin_head(pts, offsets, group, desc, n_xyz, thr, u, seed, tile_ids)
+    if out_pts.dim() != 2 or out_pts.shape[1] != 3:
+        raise HipLibraryError(f"out_pts must be [capacity, 3] (got {tuple(out_pts.shape)})")
+    capacity = int(out_pts.shape[0]) if capacity is None else int(capacity)
+    if capacity > out_pts.shape[0]:
+        raise HipLibraryError("capacity exceeds the rows of out_pts")
+    if labels is not None and labels.numel() != total:
+        raise HipLibraryError("labels and pts disagree in length")
+    if any(t is not None and t.numel() < capacity for t in (out_labels, out_src, out_key)):
+        raise HipLibraryError("out_labels / out_src / out_key are shorter than out_pts")
+    rc = load().sn_thin_scatter(_ptr(pts, torch.float64, "pts"), _ptr(labels, torch.float64, "labels"), *head,
+                                _ptr(ws, None, "ws"), ws.numel() * ws.element_size(), capacity,
+                                _ptr(out_pts, torch.float64, "out_pts"), _ptr(out_labels, torch.float64, "out_labels"),
+                                _ptr(out_src, torch.int64, "out_src"), _ptr(out_key, torch.int32, "out_key"), _stream())
+    _check(rc, "sn_thin_scatter")

@@ -22,11 +22,13 @@ ArrayLike = Union[np.ndarray, torch.Tensor]
 
 @dataclass
 class PointBatch:
-    """Ragged batch of tiles resident in HBM: pts [total,3] f64, labels [total] f64 | None, offsets [B+1] i64."""
+    """Ragged batch of tiles resident in HBM: pts [total,3] f64, labels [total] f64 | None, offsets [B+1] i64.
+    tile_ids [B] i64 | None: each tile's index in its dataset, where a loader knows it (what thin_points draws by)."""
     pts: torch.Tensor
     labels: Optional[torch.Tensor]
     offsets: torch.Tensor
     sizes: Tuple[int, ...]
+    tile_ids: Optional[torch.Tensor] = None
 
     @property
     def batch(self) -> int:
