@@ -35,7 +35,7 @@ OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so
 
-$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h $(SRC)/binning.h
+$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h $(SRC)/binning.h $(SRC)/scan.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(CXXFLAGS) $(FLAGS_$*) -c $< -o $@
 

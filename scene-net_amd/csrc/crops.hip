@@ -10,7 +10,7 @@
 // literally (a NaN anywhere is false).  Tile k holds region k's members in scan order; x, y, z and the label travel as
 // 64-bit patterns.
 //
-// Shape: one WAVE per workgroup and kChunk = 1024 consecutive points per workgroup -- lane l holds x, y of the points
+// Shape: one WAVE per workgroup and kWaveChunk = 1024 consecutive points per workgroup -- lane l holds x, y of the points
 // chunk * 1024 + g * 64 + l, g = 0..15, in registers (64 VGPRs).  A workgroup of one wave has nobody to exchange with: no
 // LDS, no barrier.  Regions are outermost: lane l fetches row k0 + l of a tile of 64 regions with one vector load each, and
 // the row travels to the wave's scalar registers by v_readlane (a wave-uniform value per region, one fetch per 1024 points).
@@ -29,16 +29,18 @@
 // label and writes 32..40 B per member; per region and point 8 fp64 VALU operations.  HBM-bound up to K of a few dozen,
 // VALU-bound beyond.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
-constexpr int kLanes = 64;
-constexpr int kGroups = 16;                  // groups of 64 consecutive points held per lane
-constexpr int kChunk = kLanes * kGroups;     // points per workgroup
+using sn::kWaveLanes;     // scan.h: the chunk's geometry (kWaveGroups groups of 64 consecutive points held per lane) and
+using sn::kWaveGroups;    // the prefix kernels' (kScanItems consecutive slots per thread and step)
+using sn::kWaveChunk;
+using sn::kScanThreads;
+using sn::kScanItems;
+using sn::readlane64;
 constexpr int kMaxK = 1 << 16;
 constexpr int64_t kMaxN = (int64_t)1 << 36;  // 2^26 workgroups
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;                // consecutive slots per thread and step of the prefix kernel
 
 constexpr uint64_t kNaNBits = 0x7ff8000000000000ull;   // what a lane past the scan's end tests: in no region
 
@@ -47,11 +49,6 @@ struct Region {
     int kind;            // anything but SN_CROP_DISC / SN_CROP_BOX: empty
 };
 
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int j) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ double readlane_f64(double v, int j) {
     return __longlong_as_double((long long)readlane64((uint64_t)__double_as_longlong(v), j));
 }
@@ -118,15 +115,16 @@ __device__ __forceinline__ bool cannot_reach(const Region& R, double xlo, double
 }
 
 // smallest / largest of v over the wave, NaN left out (comparisons with a NaN are false); +inf / -inf if there is none
-__device__ __forceinline__ void wave_min_max(const uint64_t (&bits)[kGroups], double& lo, double& hi) {
+__device__ __forceinline__ void wave_min_max(const uint64_t (&bits)[kWaveGroups], double& lo, double& hi) {
     lo = __longlong_as_double(0x7ff0000000000000ll);
     hi = -lo;
 #pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
+    for (int g = 0; g < kWaveGroups; ++g) {
         const double v = __longlong_as_double((long long)bits[g]);
         lo = v < lo ? v : lo;
         hi = v > hi ? v : hi;
     }
+    // (not two sn::wave_reduce: one after the other they schedule the count and census kernels differently)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const double a = __shfl_xor(lo, off, 64), b = __shfl_xor(hi, off, 64);
@@ -137,28 +135,28 @@ __device__ __forceinline__ void wave_min_max(const uint64_t (&bits)[kGroups], do
 
 // x, y of the chunk's points as bit patterns; past the end: NaN
 __device__ __forceinline__ void load_xy(const uint64_t* __restrict__ pts, int64_t n, int64_t base, int lane,
-                                        uint64_t (&x)[kGroups], uint64_t (&y)[kGroups]) {
+                                        uint64_t (&x)[kWaveGroups], uint64_t (&y)[kWaveGroups]) {
 #pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-        const int64_t i = base + g * kLanes + lane;
+    for (int g = 0; g < kWaveGroups; ++g) {
+        const int64_t i = base + g * kWaveLanes + lane;
         const bool in = i < n;
         x[g] = in ? pts[i * 3] : kNaNBits;
         y[g] = in ? pts[i * 3 + 1] : kNaNBits;
     }
 }
 
-__global__ __launch_bounds__(kLanes) void crop_count_kernel(const uint64_t* __restrict__ pts, int64_t n,
+__global__ __launch_bounds__(kWaveLanes) void crop_count_kernel(const uint64_t* __restrict__ pts, int64_t n,
                                                             const double* __restrict__ regions,
                                                             const int32_t* __restrict__ kinds, int K, int64_t nchunks,
                                                             int64_t* __restrict__ ws) {
     const int lane = threadIdx.x;
     const int64_t chunk = blockIdx.x;
-    uint64_t x[kGroups], y[kGroups];
-    load_xy(pts, n, chunk * kChunk, lane, x, y);
+    uint64_t x[kWaveGroups], y[kWaveGroups];
+    load_xy(pts, n, chunk * kWaveChunk, lane, x, y);
     double xlo, xhi, ylo, yhi;
     wave_min_max(x, xlo, xhi);
     wave_min_max(y, ylo, yhi);
-    for (int k0 = 0; k0 < K; k0 += kLanes) {
+    for (int k0 = 0; k0 < K; k0 += kWaveLanes) {
         const Region mine = load_region(regions, kinds, K, k0 + lane);   // (k >= K: kind -1, out of reach)
         unsigned long long live = __ballot(!cannot_reach(mine, xlo, xhi, ylo, yhi));
         int mycount = 0;
@@ -168,7 +166,7 @@ __global__ __launch_bounds__(kLanes) void crop_count_kernel(const uint64_t* __re
             const Region R = broadcast(mine, j);
             int cnt = 0;
 #pragma unroll
-            for (int g = 0; g < kGroups; ++g)
+            for (int g = 0; g < kWaveGroups; ++g)
                 cnt += __popcll(__ballot(member(R, __longlong_as_double((long long)x[g]), __longlong_as_double((long long)y[g]))));
             if (lane == j) mycount = cnt;
         }
@@ -176,76 +174,24 @@ __global__ __launch_bounds__(kLanes) void crop_count_kernel(const uint64_t* __re
     }
 }
 
-// exclusive prefix of one tile of kScanThreads * items values held `items` per thread; returns the tile's total
-template <int kItems>
-__device__ __forceinline__ int64_t block_exclusive(int64_t (&v)[kItems], int64_t* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < kItems; ++q) {
-        const int64_t t = v[q];
-        v[q] = sum;
-        sum += t;
-    }
-    int64_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const int64_t t = s_wave[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();   // s_wave is written again by the next tile
-    const int64_t mine = before + incl - sum;
-#pragma unroll
-    for (int q = 0; q < kItems; ++q) v[q] += mine;
-    return total;
-}
-
 // workgroup k: ws[k][0 .. nchunks) counts -> exclusive prefixes, ws[k][nchunks] = the region's total
 __global__ __launch_bounds__(kScanThreads) void crop_prefix_kernel(int64_t* __restrict__ ws, int64_t nchunks) {
     __shared__ int64_t s_wave[kScanThreads / 64];
     int64_t* row = ws + (int64_t)blockIdx.x * (nchunks + 1);
-    int64_t carry = 0;
-    for (int64_t t0 = 0; t0 < nchunks; t0 += kScanThreads * kScanItems) {
-        const int64_t i0 = t0 + (int64_t)threadIdx.x * kScanItems;
-        int64_t v[kScanItems];
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) v[q] = i0 + q < nchunks ? row[i0 + q] : 0;
-        const int64_t total = block_exclusive<kScanItems>(v, s_wave);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q)
-            if (i0 + q < nchunks) row[i0 + q] = carry + v[q];
-        carry += total;
-    }
-    if (threadIdx.x == 0) row[nchunks] = carry;
+    const int64_t total = sn::scan_row<kScanThreads, kScanItems>(row, nchunks, s_wave);
+    if (threadIdx.x == 0) row[nchunks] = total;
 }
 
 // one workgroup: offsets[k] = members of the regions before k, offsets[K] = all
 __global__ __launch_bounds__(kScanThreads) void crop_offsets_kernel(const int64_t* __restrict__ ws, int64_t nchunks, int K,
                                                                     int64_t* __restrict__ offsets) {
     __shared__ int64_t s_wave[kScanThreads / 64];
-    int64_t carry = 0;
-    for (int k0 = 0; k0 < K; k0 += kScanThreads) {
-        const int k = k0 + threadIdx.x;
-        int64_t v[1] = {k < K ? ws[(int64_t)k * (nchunks + 1) + nchunks] : 0};
-        const int64_t total = block_exclusive<1>(v, s_wave);
-        if (k < K) offsets[k] = carry + v[0];
-        carry += total;
-    }
-    if (threadIdx.x == 0) offsets[K] = carry;
+    sn::totals_to_offsets<kScanThreads>(ws, nchunks + 1, nchunks, K, offsets, s_wave);
 }
 
 // (waves_per_eu 3: left alone the allocator takes 170 VGPRs, two over the limit of three waves per SIMD; at 168 it still
 // needs no scratch -- at four waves it would -- and the scatter, which waits on HBM, is 8-15 % faster on the part)
-__global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(3))) void crop_scatter_kernel(const uint64_t* __restrict__ pts,
+__global__ __launch_bounds__(kWaveLanes) __attribute__((amdgpu_waves_per_eu(3))) void crop_scatter_kernel(const uint64_t* __restrict__ pts,
                                                               const uint64_t* __restrict__ labels, int64_t n,
                                                               const double* __restrict__ regions,
                                                               const int32_t* __restrict__ kinds, int K, int64_t nchunks,
@@ -254,10 +200,10 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(3))) voi
                                                               uint64_t* __restrict__ out_pts, uint64_t* __restrict__ out_labels,
                                                               int64_t* __restrict__ out_src) {
     const int lane = threadIdx.x;
-    const int64_t chunk = blockIdx.x, base = chunk * kChunk;
-    uint64_t x[kGroups], y[kGroups];
+    const int64_t chunk = blockIdx.x, base = chunk * kWaveChunk;
+    uint64_t x[kWaveGroups], y[kWaveGroups];
     load_xy(pts, n, base, lane, x, y);
-    for (int k0 = 0; k0 < K; k0 += kLanes) {
+    for (int k0 = 0; k0 < K; k0 += kWaveLanes) {
         const int k = k0 + lane;
         const Region mine = load_region(regions, kinds, K, k);
         int64_t myfirst = 0, mycount = 0;
@@ -275,15 +221,13 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(3))) voi
             const Region R = broadcast(mine, j);
             int64_t row = (int64_t)readlane64((uint64_t)myfirst, j);
 #pragma unroll
-            for (int g = 0; g < kGroups; ++g) {
+            for (int g = 0; g < kWaveGroups; ++g) {
                 const bool in = member(R, __longlong_as_double((long long)x[g]), __longlong_as_double((long long)y[g]));
                 const unsigned long long mask = __ballot(in);
                 if (in) {
-                    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-                    const int64_t o = row + rank;
+                    const int64_t o = row + sn::wave_rank(mask);
                     if ((uint64_t)o < (uint64_t)capacity) {   // (also keeps a workspace that is not this call's inside the buffer)
-                        const int64_t i = base + g * kLanes + lane;
+                        const int64_t i = base + g * kWaveLanes + lane;
                         uint64_t* p = out_pts + o * 3;
                         p[0] = x[g];
                         p[1] = y[g];
@@ -319,36 +263,28 @@ constexpr int kCensusShards = 8;
 
 using sn::enc_f64;   // common.h: the encoding K1's boxes use
 using sn::dec_f64;
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = (uint64_t)__shfl_xor((long long)v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 template <bool kLabels>
-__global__ __launch_bounds__(kLanes) void crop_census_kernel(const uint64_t* __restrict__ pts,
+__global__ __launch_bounds__(kWaveLanes) void crop_census_kernel(const uint64_t* __restrict__ pts,
                                                              const double* __restrict__ labels, int64_t n,
                                                              const double* __restrict__ regions,
                                                              const int32_t* __restrict__ kinds, int K,
                                                              const double* __restrict__ watch, int C,
                                                              unsigned long long* __restrict__ ws) {
     const int lane = threadIdx.x;
-    const int64_t base = (int64_t)blockIdx.x * kChunk;
+    const int64_t base = (int64_t)blockIdx.x * kWaveChunk;
     const int S = C + 4;   // words per region
-    uint64_t x[kGroups], y[kGroups];
+    uint64_t x[kWaveGroups], y[kWaveGroups];
     load_xy(pts, n, base, lane, x, y);
-    uint64_t code[kGroups];    // enc of the label; 0: NaN (or no label)
-    uint32_t flags[kGroups];
+    uint64_t code[kWaveGroups];    // enc of the label; 0: NaN (or no label)
+    uint32_t flags[kWaveGroups];
     if (kLabels) {
         // lane c holds watch range c; a lane without one holds (NaN, NaN): matches nothing, and is never asked for
         const double nan = __longlong_as_double((long long)kNaNBits);
         const double wlo = lane < C ? watch[2 * lane] : nan, whi = lane < C ? watch[2 * lane + 1] : nan;
 #pragma unroll
-        for (int g = 0; g < kGroups; ++g) {
-            const int64_t i = base + g * kLanes + lane;
+        for (int g = 0; g < kWaveGroups; ++g) {
+            const int64_t i = base + g * kWaveLanes + lane;
             const double l = i < n ? labels[i] : nan;   // (past the end: in no region, never counted)
             const bool isnan = l != l;
             code[g] = isnan ? 0ull : enc_f64(l);
@@ -357,7 +293,7 @@ __global__ __launch_bounds__(kLanes) void crop_census_kernel(const uint64_t* __r
         for (int c = 0; c < C; ++c) {
             const double lo = readlane_f64(wlo, c), hi = readlane_f64(whi, c);
 #pragma unroll
-            for (int g = 0; g < kGroups; ++g) {
+            for (int g = 0; g < kWaveGroups; ++g) {
                 const double l = dec_f64(code[g]);      // (code 0 decodes to a NaN: in no range)
                 flags[g] |= (lo <= l && l <= hi) ? (1u << c) : 0u;
             }
@@ -366,7 +302,7 @@ __global__ __launch_bounds__(kLanes) void crop_census_kernel(const uint64_t* __r
     double xlo, xhi, ylo, yhi;
     wave_min_max(x, xlo, xhi);
     wave_min_max(y, ylo, yhi);
-    for (int k0 = 0; k0 < K; k0 += kLanes) {
+    for (int k0 = 0; k0 < K; k0 += kWaveLanes) {
         const Region mine = load_region(regions, kinds, K, k0 + lane);   // (k >= K: kind -1, out of reach)
         unsigned long long live = __ballot(!cannot_reach(mine, xlo, xhi, ylo, yhi));
         while (live) {
@@ -377,7 +313,7 @@ __global__ __launch_bounds__(kLanes) void crop_census_kernel(const uint64_t* __r
             uint64_t mine_val = 0;      // lane t: word t of the region's row, this chunk's share
             uint64_t vmax = 0, vminc = 0;
 #pragma unroll
-            for (int g = 0; g < kGroups; ++g) {
+            for (int g = 0; g < kWaveGroups; ++g) {
                 const bool in = member(R, __longlong_as_double((long long)x[g]), __longlong_as_double((long long)y[g]));
                 const unsigned long long mask = __ballot(in);
                 if (mask == 0) continue;
@@ -399,8 +335,9 @@ __global__ __launch_bounds__(kLanes) void crop_census_kernel(const uint64_t* __r
             if (lane == 0) mine_val = (uint64_t)cnt;
             if (lane == 1) mine_val = (uint64_t)cnan;
             if (kLabels && cnt != cnan) {
-                vmax = wave_max_u64(vmax);
-                vminc = wave_max_u64(vminc);
+                const auto larger = [](uint64_t mine, uint64_t other) { return other > mine ? other : mine; };
+                vmax = sn::wave_reduce(vmax, larger);
+                vminc = sn::wave_reduce(vminc, larger);
                 if (lane == 2 + C) mine_val = vminc;
                 if (lane == 3 + C) mine_val = vmax;
             }
@@ -443,7 +380,7 @@ __global__ __launch_bounds__(kScanThreads) void crop_census_decode_kernel(const 
 }
 
 bool shape_served(int64_t n, int K) { return n > 0 && K > 0 && n <= kMaxN && K <= kMaxK; }
-int64_t host_nchunks(int64_t n) { return (n + kChunk - 1) / kChunk; }
+int64_t host_nchunks(int64_t n) { return (n + kWaveChunk - 1) / kWaveChunk; }
 
 // the checks both entries share; `what` names the entry in the error text
 int check_common(const char* what, const void* pts, int64_t n, const void* regions, const void* kinds, int K, const void* ws,
@@ -472,7 +409,7 @@ extern "C" size_t sn_crops_ws_bytes(int64_t n, int K) {
     return (size_t)K * (size_t)(host_nchunks(n) + 1) * sizeof(int64_t);
 }
 
-extern "C" int sn_crops_chunk_points(void) { return kChunk; }
+extern "C" int sn_crops_chunk_points(void) { return kWaveChunk; }
 
 extern "C" int sn_crop_count(const double* pts, int64_t n, const double* regions, const int32_t* kinds, int K, void* ws,
                              size_t ws_bytes, int64_t* offsets, sn_stream_t stream) {
@@ -481,7 +418,7 @@ extern "C" int sn_crop_count(const double* pts, int64_t n, const double* regions
     hipStream_t s = sn::as_stream(stream);
     const int64_t nchunks = host_nchunks(n);
     int64_t* w = static_cast<int64_t*>(ws);
-    hipLaunchKernelGGL(crop_count_kernel, dim3((unsigned)nchunks), dim3(kLanes), 0, s,
+    hipLaunchKernelGGL(crop_count_kernel, dim3((unsigned)nchunks), dim3(kWaveLanes), 0, s,
                        reinterpret_cast<const uint64_t*>(pts), n, regions, kinds, K, nchunks, w);
     hipLaunchKernelGGL(crop_prefix_kernel, dim3((unsigned)K), dim3(kScanThreads), 0, s, w, nchunks);
     hipLaunchKernelGGL(crop_offsets_kernel, dim3(1), dim3(kScanThreads), 0, s, w, nchunks, K, offsets);
@@ -501,7 +438,7 @@ extern "C" int sn_crop_scatter(const double* pts, const double* labels, int64_t 
     if ((uintptr_t)labels % 8 || (uintptr_t)out_pts % 8 || (uintptr_t)out_labels % 8 || (uintptr_t)out_src % 8)
         return sn::fail(SN_ERR_INVALID_ARG, "sn_crop_scatter: labels / out_pts / out_labels / out_src must be 8-byte aligned");
     const int64_t nchunks = host_nchunks(n);
-    hipLaunchKernelGGL(crop_scatter_kernel, dim3((unsigned)nchunks), dim3(kLanes), 0, sn::as_stream(stream),
+    hipLaunchKernelGGL(crop_scatter_kernel, dim3((unsigned)nchunks), dim3(kWaveLanes), 0, sn::as_stream(stream),
                        reinterpret_cast<const uint64_t*>(pts), reinterpret_cast<const uint64_t*>(labels), n, regions, kinds, K,
                        nchunks, static_cast<const int64_t*>(ws), offsets, capacity, reinterpret_cast<uint64_t*>(out_pts),
                        reinterpret_cast<uint64_t*>(out_labels), out_src);
@@ -517,7 +454,7 @@ extern "C" size_t sn_crop_census_ws_bytes(int64_t n, int K, int C) {
     return (size_t)kCensusShards * (size_t)K * (size_t)(C + 4) * sizeof(uint64_t);
 }
 
-extern "C" int sn_census_chunk_points(void) { return kChunk; }
+extern "C" int sn_census_chunk_points(void) { return kWaveChunk; }
 
 extern "C" int sn_crop_census(const double* pts, const double* labels, int64_t n, const double* regions, const int32_t* kinds,
                               int K, const double* watch, int C, void* ws, size_t ws_bytes, int64_t* counts,
@@ -550,10 +487,10 @@ extern "C" int sn_crop_census(const double* pts, const double* labels, int64_t n
         return sn::fail(SN_ERR_LAUNCH, "%s: hipMemsetAsync failed", what);
     const int64_t nchunks = host_nchunks(n);
     if (labels)
-        hipLaunchKernelGGL(crop_census_kernel<true>, dim3((unsigned)nchunks), dim3(kLanes), 0, s,
+        hipLaunchKernelGGL(crop_census_kernel<true>, dim3((unsigned)nchunks), dim3(kWaveLanes), 0, s,
                            reinterpret_cast<const uint64_t*>(pts), labels, n, regions, kinds, K, watch, C, w);
     else
-        hipLaunchKernelGGL(crop_census_kernel<false>, dim3((unsigned)nchunks), dim3(kLanes), 0, s,
+        hipLaunchKernelGGL(crop_census_kernel<false>, dim3((unsigned)nchunks), dim3(kWaveLanes), 0, s,
                            reinterpret_cast<const uint64_t*>(pts), labels, n, regions, kinds, K, watch, C, w);
     hipLaunchKernelGGL(crop_census_decode_kernel, dim3((unsigned)((K + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, s,
                        w, K, C, counts, label_range);

@@ -38,6 +38,7 @@
 // 32-byte row load that the lane waits for; measured 1.3e11 tests/s in the union, about 3 % of the part's fp64 vector
 // rate.  The others by HBM / L2 latency.
 #include "common.h"
+#include "scan.h"
 #include <cmath>
 
 namespace {
@@ -46,7 +47,7 @@ constexpr int kThreads = 256;
 constexpr int kSelGroups = 4;
 constexpr int kSelChunk = kThreads * kSelGroups;   // scan points per workgroup of the select kernels
 constexpr int kRankChunk = kThreads;               // positions per workgroup of launches 1, 3..6, 8
-constexpr int kScanThreads = 1024;
+constexpr int kScanThreads = 1024;                 // the one-workgroup prefix kernels (their own tile, not scan.h's)
 constexpr int kScanItems = 4;
 constexpr int kMaxKeep = 64;
 constexpr int64_t kMaxN = (int64_t)1 << 33;
@@ -141,28 +142,6 @@ __device__ __forceinline__ void for_candidates(const CellGrid& g, const int32_t*
         }
 }
 
-// exclusive prefix of one value per thread over the workgroup; returns the total.  s_wave: blockDim.x / 64 slots
-__device__ __forceinline__ int64_t block_exclusive(int64_t v, int64_t* s_wave, int64_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-    int64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t before = 0;
-    total = 0;
-    for (int w = 0; w < waves; ++w) {
-        const int64_t t = s_wave[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();   // s_wave is written again by the next tile
-    return before + incl - v;
-}
-
 // ------------------------------------------------------------------------------------------------------------- select
 __device__ __forceinline__ bool is_selected(const double* __restrict__ labels, const double* __restrict__ keep, int n_keep,
                                             int64_t i) {
@@ -246,10 +225,10 @@ __global__ __launch_bounds__(kScanThreads) void select_prefix_kernel(int64_t* __
     double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
     for (int64_t t0 = 0; t0 < nchunks; t0 += kScanThreads) {
         const int64_t c = t0 + threadIdx.x;
-        int64_t total;
-        const int64_t before = block_exclusive(c < nchunks ? counts[c] : 0, s_wave, total);
+        int64_t v[1] = {c < nchunks ? counts[c] : 0};
+        const int64_t total = sn::block_exclusive<kScanThreads, 1>(v, s_wave);
         if (c < nchunks) {
-            counts[c] = carry + before;
+            counts[c] = carry + v[0];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 const double l = boxes[c * 6 + a], h = boxes[c * 6 + 3 + a];
@@ -297,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void select_scatter_kernel(const double* 
         const int64_t i = base + g * kThreads + threadIdx.x;
         in[g] = i < n && is_selected(labels, keep, n_keep, i);
         const unsigned long long mask = __ballot(in[g]);
-        rank[g] = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+        rank[g] = sn::wave_rank(mask);
         if ((threadIdx.x & 63) == 0) s_cnt[g * (kThreads / 64) + wave] = __popcll(mask);
     }
     __syncthreads();
@@ -337,21 +316,15 @@ __global__ __launch_bounds__(kScanThreads) void dbscan_prefix_kernel(int32_t* __
     int64_t carry = 0;
     for (int t0 = 0; t0 < cells; t0 += kScanThreads * kScanItems) {
         const int c0 = t0 + threadIdx.x * kScanItems;
-        int v[kScanItems];
-        int64_t sum = 0;
+        int64_t v[kScanItems];
 #pragma unroll
-        for (int q = 0; q < kScanItems; ++q) {
-            v[q] = c0 + q < cells ? pop[c0 + q] : 0;
-            sum += v[q];
-        }
-        int64_t total;
-        int64_t run = carry + block_exclusive(sum, s_wave, total);
+        for (int q = 0; q < kScanItems; ++q) v[q] = c0 + q < cells ? pop[c0 + q] : 0;
+        const int64_t total = sn::block_exclusive<kScanThreads, kScanItems>(v, s_wave);
 #pragma unroll
         for (int q = 0; q < kScanItems; ++q)
             if (c0 + q < cells) {
-                start[c0 + q] = (int32_t)run;
-                pop[c0 + q] = (int32_t)run;
-                run += v[q];
+                start[c0 + q] = (int32_t)(carry + v[q]);
+                pop[c0 + q] = (int32_t)(carry + v[q]);
             }
         carry += total;
     }
@@ -480,8 +453,7 @@ __global__ __launch_bounds__(kThreads) void dbscan_flatten_kernel(const int64_t*
         if (w < wave) before += s_cnt[w];
         total += s_cnt[w];
     }
-    if (is_root)
-        root_rank[i] = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+    if (is_root) root_rank[i] = before + sn::wave_rank(mask);
     if (threadIdx.x == 0) chunk_roots[blockIdx.x] = total;
 }
 
@@ -489,17 +461,11 @@ __global__ __launch_bounds__(kThreads) void dbscan_flatten_kernel(const int64_t*
 __global__ __launch_bounds__(kScanThreads) void dbscan_rank_kernel(int32_t* __restrict__ chunk_roots, int nchunks,
                                                                    int max_clusters, int32_t* __restrict__ n_clusters,
                                                                    long long* __restrict__ stats) {
-    __shared__ int64_t s_wave[kScanThreads / 64];
-    int64_t carry = 0;
-    for (int t0 = 0; t0 < nchunks; t0 += kScanThreads) {
-        const int c = t0 + threadIdx.x;
-        int64_t total;
-        const int64_t before = block_exclusive(c < nchunks ? chunk_roots[c] : 0, s_wave, total);
-        if (c < nchunks) chunk_roots[c] = (int32_t)(carry + before);
-        carry += total;
-    }
+    __shared__ int32_t s_wave[kScanThreads / 64];
+    // (int32 throughout, as the slots are: the roots are positions, fewer than 2^31)
+    const int32_t roots = sn::scan_row<kScanThreads, 1>(chunk_roots, nchunks, s_wave);
     for (int i = threadIdx.x; i < max_clusters * SN_DBSCAN_NSTAT; i += kScanThreads) stats[i] = 0;
-    if (threadIdx.x == 0) *n_clusters = (int32_t)carry;
+    if (threadIdx.x == 0) *n_clusters = roots;
 }
 
 // ---- 8: labels and statistics

@@ -9,8 +9,8 @@
 // (binning.h: the text voxel.hip bins with).  u is the caller's, or Philox4x32-10 of (seed; j, tile id): a function of
 // the point's place in ITS tile, never of the batch or of scheduling.
 //
-// Shape: K9's -- one WAVE per workgroup, kChunk = 1024 consecutive rows of the packed batch per workgroup, lane l holding
-// the rows chunk * 1024 + g * 64 + l, g = 0..15.  A chunk may straddle tiles: the wave finds the tile of its first row by
+// Shape: K9's, its scans and ranks from scan.h -- one WAVE per workgroup, kWaveChunk = 1024 consecutive rows of the packed
+// batch per workgroup, lane l holding the rows chunk * 1024 + g * 64 + l, g = 0..15.  A chunk may straddle tiles: the wave finds the tile of its first row by
 // a bisection of offsets (wave-uniform, scalar loads) and walks the tiles that reach into the chunk, one edge table in LDS
 // at a time (one wave: the barrier around the reload costs nothing).
 //   count:    the decision of every row -> ws.keep[chunk][16] (one 64-bit ballot per group), ws.unb[chunk][16] (rows that
@@ -28,16 +28,17 @@
 // gathered 8 B of thr; scatter reads 24 + 8 B and writes 24 + 8 + 8 (+ 4) B per kept row.
 #include "common.h"
 #include "binning.h"
+#include "scan.h"
 
 namespace {
 
-constexpr int kLanes = 64;
-constexpr int kGroups = 16;                  // groups of 64 consecutive rows held per lane
-constexpr int kChunk = kLanes * kGroups;     // rows per workgroup
+using sn::kWaveLanes;     // scan.h: kWaveGroups groups of 64 consecutive rows held per lane, kWaveChunk rows per workgroup
+using sn::kWaveGroups;
+using sn::kWaveChunk;
+using sn::kScanThreads;
+using sn::kScanItems;
 constexpr int kMaxB = 1 << 16;
 constexpr int64_t kMaxTotal = (int64_t)1 << 33;
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;
 
 // ---- Philox4x32-10 (Salmon et al., SC'11; the constants of Random123's philox.h)
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
@@ -98,14 +99,14 @@ __device__ __forceinline__ void first_min(unsigned long long* slot, unsigned lon
 // first (kFirst): atomic min of the in-tile index over every BINNED row of a group, kept or not.
 template <int kGroup, bool kKey, bool kFirst>
 __device__ __forceinline__ void decide_chunk(const Rule& R, int64_t base, int lane, double* edges, uint32_t& keep,
-                                             uint32_t& unb, int (&key)[kGroups], unsigned long long* __restrict__ first) {
+                                             uint32_t& unb, int (&key)[kWaveGroups], unsigned long long* __restrict__ first) {
     keep = 0u;
     unb = 0u;
     if (kKey) {
 #pragma unroll
-        for (int g = 0; g < kGroups; ++g) key[g] = -1;
+        for (int g = 0; g < kWaveGroups; ++g) key[g] = -1;
     }
-    const int64_t end = base + kChunk < R.total ? base + kChunk : R.total;
+    const int64_t end = base + kWaveChunk < R.total ? base + kWaveChunk : R.total;
     const uint64_t seed = R.seed ? *R.seed : 0ull;
     const int ne = R.nx + R.ny + R.nz + 3;
     const int plane = R.nx * R.ny;
@@ -118,7 +119,7 @@ __device__ __forceinline__ void decide_chunk(const Rule& R, int64_t base, int la
         if (kGroup != SN_THIN_GROUP_NONE) {
             const double* d = R.desc + (size_t)b * (size_t)(6 + ne);
             __syncthreads();   // the previous tile's table has been read
-            sn::load_edges(edges, d, ne, kLanes);
+            sn::load_edges(edges, d, ne, kWaveLanes);
             bin.init(edges, d, R.nx, R.ny, R.nz);
         }
         const uint64_t t = R.tile_ids ? (uint64_t)R.tile_ids[b] : (uint64_t)b;
@@ -128,15 +129,15 @@ __device__ __forceinline__ void decide_chunk(const Rule& R, int64_t base, int la
         // share to memory ([measured] 10^7 rows looking at the same 64 words of memory: 7x the count without `first`)
         unsigned long long* lfirst = reinterpret_cast<unsigned long long*>(edges + ne);
         if (kFirst && kGroup == SN_THIN_GROUP_Z && fst) {
-            for (int k = lane; k < R.nz; k += kLanes) lfirst[k] = ~0ull;
+            for (int k = lane; k < R.nz; k += kWaveLanes) lfirst[k] = ~0ull;
             __syncthreads();
         }
         // without groups the tile's first row is its row 0: the one lane that holds it says so
-        if (kFirst && kGroup == SN_THIN_GROUP_NONE && fst && lo >= base && (int)((lo - base) & (kLanes - 1)) == lane)
+        if (kFirst && kGroup == SN_THIN_GROUP_NONE && fst && lo >= base && (int)((lo - base) & (kWaveLanes - 1)) == lane)
             fst[0] = 0ull;
 #pragma unroll
-        for (int g = 0; g < kGroups; ++g) {
-            const int64_t i = base + g * kLanes + lane;
+        for (int g = 0; g < kWaveGroups; ++g) {
+            const int64_t i = base + g * kWaveLanes + lane;
             if (i < from || i >= to) continue;
             int grp = 0;
             if (kGroup != SN_THIN_GROUP_NONE) {
@@ -159,7 +160,7 @@ __device__ __forceinline__ void decide_chunk(const Rule& R, int64_t base, int la
         }
         if (kFirst && kGroup == SN_THIN_GROUP_Z && fst) {
             __syncthreads();
-            for (int k = lane; k < R.nz; k += kLanes)
+            for (int k = lane; k < R.nz; k += kWaveLanes)
                 if (lfirst[k] != ~0ull) first_min(fst + k, lfirst[k]);
         }
     }
@@ -178,23 +179,23 @@ __host__ __device__ inline Ws ws_of(void* ws, int64_t nchunks) {
     r.kept = w;
     r.lost = w + (nchunks + 1);
     r.keep = reinterpret_cast<uint64_t*>(w + 2 * (nchunks + 1));
-    r.unb = r.keep + nchunks * kGroups;
+    r.unb = r.keep + nchunks * kWaveGroups;
     return r;
 }
 
 template <int kGroup>
-__global__ __launch_bounds__(kLanes) void thin_count_kernel(Rule R, int64_t nchunks, void* __restrict__ ws_raw,
+__global__ __launch_bounds__(kWaveLanes) void thin_count_kernel(Rule R, int64_t nchunks, void* __restrict__ ws_raw,
                                                             unsigned long long* __restrict__ first) {
     extern __shared__ double edges[];
     const int lane = threadIdx.x;
     const int64_t chunk = blockIdx.x;
     uint32_t keep, unb;
-    int key[kGroups];
-    decide_chunk<kGroup, false, true>(R, chunk * kChunk, lane, edges, keep, unb, key, first);
+    int key[kWaveGroups];
+    decide_chunk<kGroup, false, true>(R, chunk * kWaveChunk, lane, edges, keep, unb, key, first);
     uint64_t mine_keep = 0, mine_unb = 0;
     int nkeep = 0, nunb = 0;
 #pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
+    for (int g = 0; g < kWaveGroups; ++g) {
         const unsigned long long mk = __ballot((keep >> g) & 1u), mu = __ballot((unb >> g) & 1u);
         nkeep += __popcll(mk);
         nunb += __popcll(mu);
@@ -204,9 +205,9 @@ __global__ __launch_bounds__(kLanes) void thin_count_kernel(Rule R, int64_t nchu
         }
     }
     const Ws w = ws_of(ws_raw, nchunks);
-    if (lane < kGroups) {
-        w.keep[chunk * kGroups + lane] = mine_keep;
-        w.unb[chunk * kGroups + lane] = mine_unb;
+    if (lane < kWaveGroups) {
+        w.keep[chunk * kWaveGroups + lane] = mine_keep;
+        w.unb[chunk * kWaveGroups + lane] = mine_unb;
     }
     if (lane == 0) {
         w.kept[chunk] = nkeep;
@@ -214,67 +215,23 @@ __global__ __launch_bounds__(kLanes) void thin_count_kernel(Rule R, int64_t nchu
     }
 }
 
-// exclusive prefix of one tile of kScanThreads * items values held `items` per thread; returns the tile's total (K9's)
-template <int kItems>
-__device__ __forceinline__ int64_t block_exclusive(int64_t (&v)[kItems], int64_t* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < kItems; ++q) {
-        const int64_t t = v[q];
-        v[q] = sum;
-        sum += t;
-    }
-    int64_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const int64_t t = s_wave[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();   // s_wave is written again by the next tile
-    const int64_t mine = before + incl - sum;
-#pragma unroll
-    for (int q = 0; q < kItems; ++q) v[q] += mine;
-    return total;
-}
-
 // workgroup r (0: kept, 1: lost): row[0 .. nchunks) counts -> exclusive prefixes, row[nchunks] = the total
 __global__ __launch_bounds__(kScanThreads) void thin_prefix_kernel(int64_t* __restrict__ ws, int64_t nchunks) {
     __shared__ int64_t s_wave[kScanThreads / 64];
     int64_t* row = ws + (int64_t)blockIdx.x * (nchunks + 1);
-    int64_t carry = 0;
-    for (int64_t t0 = 0; t0 < nchunks; t0 += kScanThreads * kScanItems) {
-        const int64_t i0 = t0 + (int64_t)threadIdx.x * kScanItems;
-        int64_t v[kScanItems];
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) v[q] = i0 + q < nchunks ? row[i0 + q] : 0;
-        const int64_t total = block_exclusive<kScanItems>(v, s_wave);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q)
-            if (i0 + q < nchunks) row[i0 + q] = carry + v[q];
-        carry += total;
-    }
-    if (threadIdx.x == 0) row[nchunks] = carry;
+    const int64_t total = sn::scan_row<kScanThreads, kScanItems>(row, nchunks, s_wave);
+    if (threadIdx.x == 0) row[nchunks] = total;
 }
 
 // set bits of `mask` [nchunks][16] in front of packed index p (clamped to 0 .. total), given the chunks' prefixes
 __device__ __forceinline__ int64_t bits_before(const int64_t* __restrict__ prefix, const uint64_t* __restrict__ mask,
                                                int64_t nchunks, int64_t total, int64_t p) {
     p = p < 0 ? 0 : (p > total ? total : p);
-    const int64_t c = p / kChunk;
+    const int64_t c = p / kWaveChunk;
     if (c >= nchunks) return prefix[nchunks];   // p == total on a chunk seam
-    const int r = (int)(p - c * kChunk), full = r >> 6, rest = r & 63;
+    const int r = (int)(p - c * kWaveChunk), full = r >> 6, rest = r & 63;
     int64_t n = prefix[c];
-    const uint64_t* m = mask + c * kGroups;
+    const uint64_t* m = mask + c * kWaveGroups;
     for (int q = 0; q < full; ++q) n += __popcll(m[q]);
     if (rest) n += __popcll(m[full] & ((1ull << rest) - 1ull));
     return n;
@@ -296,25 +253,24 @@ __global__ __launch_bounds__(kScanThreads) void thin_offsets_kernel(const int64_
 
 // kDecide: the decision is made again (and the groups found for out_key); otherwise the count's ballots are read
 template <int kGroup, bool kDecide>
-__global__ __launch_bounds__(kLanes) void thin_scatter_kernel(Rule R, const uint64_t* __restrict__ labels, int64_t nchunks,
+__global__ __launch_bounds__(kWaveLanes) void thin_scatter_kernel(Rule R, const uint64_t* __restrict__ labels, int64_t nchunks,
                                                               void* __restrict__ ws_raw, int64_t capacity,
                                                               uint64_t* __restrict__ out_pts, uint64_t* __restrict__ out_labels,
                                                               int64_t* __restrict__ out_src, int32_t* __restrict__ out_key) {
     extern __shared__ double edges[];
     const int lane = threadIdx.x;
-    const int64_t chunk = blockIdx.x, base = chunk * kChunk;
+    const int64_t chunk = blockIdx.x, base = chunk * kWaveChunk;
     const Ws w = ws_of(ws_raw, nchunks);
     uint32_t keep = 0u, unb = 0u;
-    int key[kGroups];
+    int key[kWaveGroups];
     if (kDecide) decide_chunk<kGroup, true, false>(R, base, lane, edges, keep, unb, key, nullptr);
     int64_t row = w.kept[chunk];
 #pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-        const unsigned long long mask = kDecide ? __ballot((keep >> g) & 1u) : w.keep[chunk * kGroups + g];
+    for (int g = 0; g < kWaveGroups; ++g) {
+        const unsigned long long mask = kDecide ? __ballot((keep >> g) & 1u) : w.keep[chunk * kWaveGroups + g];
         if ((mask >> lane) & 1ull) {
-            const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-            const int64_t o = row + rank;
-            const int64_t i = base + g * kLanes + lane;
+            const int64_t o = row + sn::wave_rank(mask);
+            const int64_t i = base + g * kWaveLanes + lane;
             // (both tests also keep a workspace that is not this call's inside the buffers)
             if ((uint64_t)o < (uint64_t)capacity && i < R.total) {
                 const uint64_t* p = R.pts + i * 3;
@@ -331,7 +287,7 @@ __global__ __launch_bounds__(kLanes) void thin_scatter_kernel(Rule R, const uint
     }
 }
 
-int64_t host_nchunks(int64_t total) { return (total + kChunk - 1) / kChunk; }
+int64_t host_nchunks(int64_t total) { return (total + kWaveChunk - 1) / kWaveChunk; }
 bool shape_served(int64_t total, int B) { return total > 0 && B > 0 && total <= kMaxTotal && B <= kMaxB; }
 
 // the checks both entries share; `what` names the entry in the error text.  On SN_OK `R` is filled and `lds` set.
@@ -394,10 +350,10 @@ int check_common(const char* what, const double* pts, const int64_t* offsets, in
 extern "C" size_t sn_thin_ws_bytes(int64_t total, int B) {
     if (!shape_served(total, B)) return 0;
     const int64_t nchunks = host_nchunks(total);
-    return (size_t)(2 * (nchunks + 1) + 2 * nchunks * kGroups) * sizeof(int64_t);
+    return (size_t)(2 * (nchunks + 1) + 2 * nchunks * kWaveGroups) * sizeof(int64_t);
 }
 
-extern "C" int sn_thin_chunk_points(void) { return kChunk; }
+extern "C" int sn_thin_chunk_points(void) { return kWaveChunk; }
 
 extern "C" int sn_thin_count(const double* pts, const int64_t* offsets, int64_t total, int B, int group, const double* desc,
                              int nx, int ny, int nz, const double* thr, const double* u, const uint64_t* seed,
@@ -418,7 +374,7 @@ extern "C" int sn_thin_count(const double* pts, const int64_t* offsets, int64_t 
         return sn::fail(SN_ERR_LAUNCH, "%s: hipMemsetAsync failed", what);
     const int64_t nchunks = host_nchunks(total);
     unsigned long long* f = reinterpret_cast<unsigned long long*>(first);
-    const dim3 grid((unsigned)nchunks), block(kLanes);
+    const dim3 grid((unsigned)nchunks), block(kWaveLanes);
     if (group == SN_THIN_GROUP_NONE)
         hipLaunchKernelGGL(thin_count_kernel<SN_THIN_GROUP_NONE>, grid, block, 0, s, R, nchunks, ws, f);
     else if (group == SN_THIN_GROUP_Z)
@@ -451,7 +407,7 @@ extern "C" int sn_thin_scatter(const double* pts, const double* labels, const in
                         what);
     const int64_t nchunks = host_nchunks(total);
     hipStream_t s = sn::as_stream(stream);
-    const dim3 grid((unsigned)nchunks), block(kLanes);
+    const dim3 grid((unsigned)nchunks), block(kWaveLanes);
     void* w = const_cast<void*>(ws);   // (read only: ws_of serves both kernels)
     const uint64_t* lab = reinterpret_cast<const uint64_t*>(labels);
     uint64_t* op = reinterpret_cast<uint64_t*>(out_pts);

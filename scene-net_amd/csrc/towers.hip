@@ -23,6 +23,7 @@
 //
 // Bound: launches 1 and 6 by HBM (the grid read once, the labels written once); 2, 3 by LDS / L2 reads per positive voxel.
 #include "common.h"
+#include "scan.h"
 #include <cmath>
 #include <type_traits>
 
@@ -273,27 +274,16 @@ __global__ __launch_bounds__(kRankThreads) void towers_rank_kernel(const uint64_
                                                                    int32_t* __restrict__ n_towers,
                                                                    long long* __restrict__ stats) {
     __shared__ int32_t wave_sum[kRankThreads / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const uint64_t* bits = rootbits + (size_t)b * sh.N;
     int32_t* pre = prefix + (size_t)b * sh.N;
     const int per = (sh.N + kRankThreads - 1) / kRankThreads;   // a contiguous run of words per thread
     const int w0 = min(tid * per, sh.N), w1 = min(w0 + per, sh.N);
     int32_t mine = 0;
     for (int w = w0; w < w1; ++w) mine += __popcll(bits[w]);
-    int32_t incl = mine;                                          // inclusive scan across the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int32_t base = 0, total = 0;
-    for (int q = 0; q < kRankThreads / 64; ++q) {
-        if (q < wave) base += wave_sum[q];
-        total += wave_sum[q];
-    }
-    int32_t run = base + incl - mine;
+    int32_t before[1] = {mine};
+    const int32_t total = sn::block_exclusive<kRankThreads, 1>(before, wave_sum);
+    int32_t run = before[0];                                      // roots in the words of the threads in front
     const int K = total < max_towers ? total : max_towers;
     long long* rows = stats + (size_t)b * max_towers * SN_TOWER_NSTAT;
     for (int i = tid; i < max_towers * SN_TOWER_NSTAT; i += kRankThreads) {
@@ -313,12 +303,6 @@ __global__ __launch_bounds__(kRankThreads) void towers_rank_kernel(const uint64_
         run += __popcll(m);
     }
     if (tid == 0) n_towers[b] = total;
-}
-
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // ---- 6: labels and statistics
@@ -378,7 +362,7 @@ __global__ __launch_bounds__(kThreads) void towers_finish_kernel(const uint64_t*
             const bool mine = has && id == lid;
             const uint64_t m = __ballot(mine);
             todo &= ~m;
-            const long long s2 = wave_sum_ll(mine ? (long long)i2 : 0);
+            const long long s2 = sn::wave_reduce(mine ? (long long)i2 : 0ll, [](long long a, long long b) { return a + b; });
             if (lane == leader) {
                 const unsigned long long cnt = __popcll(m);
                 const int base2 = i2 - lane;

@@ -10,8 +10,8 @@
 // with -ffp-contract=off).  ranges: a cell is live iff value > lin[1]; its colour is row argmin_j |(value - lin[j]) - step|
 // of the table (the first minimum wins), times 255.0.  Cloud b holds tile b's live cells in C order of (z, x, y).
 //
-// Shape: crops.hip's.  One WAVE per workgroup and kChunk = 1024 consecutive cells of one tile per workgroup; lane l looks at
-// the cells chunk * 1024 + g * 64 + l, g = 0..15.  Per group __ballot of the live test gives the wave-uniform __popcll
+// Shape: crops.hip's, its scans and ranks from scan.h.  One WAVE per workgroup and kWaveChunk = 1024 consecutive cells of one
+// tile per workgroup; lane l looks at the cells chunk * 1024 + g * 64 + l, g = 0..15.  Per group __ballot of the live test gives the wave-uniform __popcll
 // (count) and, in the scatter, the lane's rank by mbcnt of the same mask: output order is cell order by construction.
 //   count:   ws[b][chunk] = live cells of the chunk, and two slots per chunk for `bad` (one slot per workgroup each: no
 //            memset, no atomics)
@@ -25,17 +25,18 @@
 // VALU operations per cell in `density`, 7 r per live cell in `ranges`.  HBM-bound by design.
 #include <cfloat>
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
-constexpr int kLanes = 64;
-constexpr int kGroups = 16;                  // groups of 64 consecutive cells per workgroup
-constexpr int kChunk = kLanes * kGroups;     // cells per workgroup
+using sn::kWaveLanes;     // scan.h: kWaveGroups groups of 64 consecutive cells, kWaveChunk cells per workgroup
+using sn::kWaveGroups;
+using sn::kWaveChunk;
+using sn::kScanThreads;
+using sn::kScanItems;
 constexpr int kMaxB = 65535;                 // (tiles are the launch grid's y)
 constexpr int64_t kMaxV = ((int64_t)1 << 31) - 1;   // cells per tile: the index split is 32-bit
 constexpr int kMaxR = 32;
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;
 
 struct CloudParams {
     double lin[kMaxR];         // np.linspace(0, 1, r)
@@ -117,7 +118,7 @@ __device__ __forceinline__ bool tile_padded(const double* __restrict__ d, int n0
 __host__ __device__ __forceinline__ int64_t ws_stride(int64_t nchunks) { return 3 * nchunks + 1; }
 
 template <typename T>
-__global__ __launch_bounds__(kLanes) void cloud_count_kernel(const T* __restrict__ grid, int64_t V, int n0, int n1, int n2,
+__global__ __launch_bounds__(kWaveLanes) void cloud_count_kernel(const T* __restrict__ grid, int64_t V, int n0, int n1, int n2,
                                                              int mode, double lin1, const double* __restrict__ desc,
                                                              int desc_len, int64_t nchunks, int64_t* __restrict__ ws) {
     const int lane = threadIdx.x;
@@ -128,8 +129,8 @@ __global__ __launch_bounds__(kLanes) void cloud_count_kernel(const T* __restrict
     const bool padded = d && tile_padded(d, n0, n1, n2);
     int cnt = 0, cnan = 0, ccol = 0;
 #pragma unroll
-    for (int q = 0; q < kGroups; ++q) {
-        const int64_t n = chunk * kChunk + q * kLanes + lane;
+    for (int q = 0; q < kWaveGroups; ++q) {
+        const int64_t n = chunk * kWaveChunk + q * kWaveLanes + lane;
         const double v = n < V ? widen(g[n]) : 0.0;
         bool live = is_live(v, mode, lin1);       // (past the end: 0.0, live in neither mode -- lin1 > 0)
         if (padded && live) live = cell_in_tile(d, split((uint32_t)n, (uint32_t)n1, (uint32_t)n2), n1, n2);
@@ -149,58 +150,14 @@ __global__ __launch_bounds__(kLanes) void cloud_count_kernel(const T* __restrict
     }
 }
 
-// exclusive prefix of one tile of kScanThreads * items values held `items` per thread; returns the tile's total
-template <int kItems>
-__device__ __forceinline__ int64_t block_exclusive(int64_t (&v)[kItems], int64_t* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < kItems; ++q) {
-        const int64_t t = v[q];
-        v[q] = sum;
-        sum += t;
-    }
-    int64_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int64_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const int64_t t = s_wave[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();   // s_wave is written again by the next tile
-    const int64_t mine = before + incl - sum;
-#pragma unroll
-    for (int q = 0; q < kItems; ++q) v[q] += mine;
-    return total;
-}
-
 // workgroup b: ws[b][0 .. nchunks) counts -> exclusive prefixes, ws[b][nchunks] = the tile's total; bad[b] = the sums of
 // the chunks' slots (integers: the order of the additions is fixed and would not matter)
 __global__ __launch_bounds__(kScanThreads) void cloud_prefix_kernel(int64_t* __restrict__ ws, int64_t nchunks,
                                                                     int64_t* __restrict__ bad) {
     __shared__ int64_t s_wave[kScanThreads / 64];
     int64_t* row = ws + (int64_t)blockIdx.x * ws_stride(nchunks);
-    int64_t carry = 0;
-    for (int64_t t0 = 0; t0 < nchunks; t0 += kScanThreads * kScanItems) {
-        const int64_t i0 = t0 + (int64_t)threadIdx.x * kScanItems;
-        int64_t v[kScanItems];
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) v[q] = i0 + q < nchunks ? row[i0 + q] : 0;
-        const int64_t total = block_exclusive<kScanItems>(v, s_wave);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q)
-            if (i0 + q < nchunks) row[i0 + q] = carry + v[q];
-        carry += total;
-    }
-    if (threadIdx.x == 0) row[nchunks] = carry;
+    const int64_t live = sn::scan_row<kScanThreads, kScanItems>(row, nchunks, s_wave);
+    if (threadIdx.x == 0) row[nchunks] = live;
     // thread t sums the slots t, t + 256, ... of each kind; the block sums the threads
     const int64_t* slots = row + nchunks + 1;
     int64_t a[2] = {0, 0};
@@ -210,7 +167,7 @@ __global__ __launch_bounds__(kScanThreads) void cloud_prefix_kernel(int64_t* __r
     }
     for (int k = 0; k < 2; ++k) {
         int64_t v[1] = {a[k]};
-        const int64_t total = block_exclusive<1>(v, s_wave);
+        const int64_t total = sn::block_exclusive<kScanThreads, 1>(v, s_wave);
         if (threadIdx.x == 0) bad[2 * (int64_t)blockIdx.x + k] = total;
     }
 }
@@ -219,15 +176,7 @@ __global__ __launch_bounds__(kScanThreads) void cloud_prefix_kernel(int64_t* __r
 __global__ __launch_bounds__(kScanThreads) void cloud_offsets_kernel(const int64_t* __restrict__ ws, int64_t nchunks, int B,
                                                                      int64_t* __restrict__ offsets) {
     __shared__ int64_t s_wave[kScanThreads / 64];
-    int64_t carry = 0;
-    for (int b0 = 0; b0 < B; b0 += kScanThreads) {
-        const int b = b0 + threadIdx.x;
-        int64_t v[1] = {b < B ? ws[(int64_t)b * ws_stride(nchunks) + nchunks] : 0};
-        const int64_t total = block_exclusive<1>(v, s_wave);
-        if (b < B) offsets[b] = carry + v[0];
-        carry += total;
-    }
-    if (threadIdx.x == 0) offsets[B] = carry;
+    sn::totals_to_offsets<kScanThreads>(ws, ws_stride(nchunks), nchunks, B, offsets, s_wave);
 }
 
 // NaN -> 0
@@ -238,7 +187,7 @@ __device__ __forceinline__ uint16_t rgb16_of(double t) {
 }
 
 template <typename T, bool kRanges>
-__global__ __launch_bounds__(kLanes) void cloud_scatter_kernel(const T* __restrict__ grid, int64_t V, int n0, int n1, int n2,
+__global__ __launch_bounds__(kWaveLanes) void cloud_scatter_kernel(const T* __restrict__ grid, int64_t V, int n0, int n1, int n2,
                                                                CloudParams P, const double* __restrict__ desc, int desc_len,
                                                                int64_t nchunks, const int64_t* __restrict__ ws,
                                                                const int64_t* __restrict__ offsets, int64_t capacity,
@@ -260,8 +209,8 @@ __global__ __launch_bounds__(kLanes) void cloud_scatter_kernel(const T* __restri
     __shared__ double s_lin[kRanges ? kMaxR : 1], s_tab[kRanges ? kMaxR * 3 : 1];
     if (kRanges) stage_tables(P, lane, s_lin, s_tab);   // (behind the wave-uniform return above: one wave, nobody waits)
 #pragma unroll
-    for (int q = 0; q < kGroups; ++q) {
-        const int64_t n = chunk * kChunk + q * kLanes + lane;
+    for (int q = 0; q < kWaveGroups; ++q) {
+        const int64_t n = chunk * kWaveChunk + q * kWaveLanes + lane;
         const double v = n < V ? widen(g[n]) : 0.0;
         bool live = is_live(v, kMode, lin1);
         Split s{0, 0, 0};
@@ -271,8 +220,7 @@ __global__ __launch_bounds__(kLanes) void cloud_scatter_kernel(const T* __restri
         }
         const unsigned long long mask = __ballot(live);
         if (live) {
-            const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-            const int64_t o = row + rank;
+            const int64_t o = row + sn::wave_rank(mask);
             if ((uint64_t)o < (uint64_t)capacity) {   // (also keeps a workspace that is not this call's inside the buffers)
                 double x, y, z, cr, cg, cb;
                 if (d) {
@@ -321,7 +269,7 @@ __global__ __launch_bounds__(kLanes) void cloud_scatter_kernel(const T* __restri
     }
 }
 
-int64_t host_nchunks(int64_t V) { return (V + kChunk - 1) / kChunk; }
+int64_t host_nchunks(int64_t V) { return (V + kWaveChunk - 1) / kWaveChunk; }
 bool shape_served(int B, int64_t V) { return B > 0 && V > 0 && B <= kMaxB && V <= kMaxV; }
 
 size_t dtype_size(int dtype) {
@@ -374,7 +322,7 @@ void fill_lin(CloudParams& P, int mode, int r) {
 
 }  // namespace
 
-extern "C" int sn_voxel_cloud_chunk_cells(void) { return kChunk; }
+extern "C" int sn_voxel_cloud_chunk_cells(void) { return kWaveChunk; }
 
 extern "C" size_t sn_voxel_cloud_ws_bytes(int B, int64_t V) {
     if (!shape_served(B, V)) return 0;
@@ -397,7 +345,7 @@ extern "C" int sn_voxel_cloud_count(const void* grid, int dtype, int B, int n0, 
     int64_t* w = static_cast<int64_t*>(ws);
     const dim3 grd((unsigned)nchunks, (unsigned)B);
 #define SN_COUNT(T)                                                                                                    \
-    hipLaunchKernelGGL(cloud_count_kernel<T>, grd, dim3(kLanes), 0, s, static_cast<const T*>(grid), V, n0, n1, n2, mode, \
+    hipLaunchKernelGGL(cloud_count_kernel<T>, grd, dim3(kWaveLanes), 0, s, static_cast<const T*>(grid), V, n0, n1, n2, mode, \
                        P.lin[1], desc, dlen, nchunks, w)
     switch (dtype) {
         case SN_F32: SN_COUNT(float); break;
@@ -431,7 +379,7 @@ extern "C" int sn_voxel_cloud_scatter(const void* grid, int dtype, int B, int n0
     const int dlen = SN_DESC_LEN(n1, n2, n0);
     const dim3 grd((unsigned)nchunks, (unsigned)B);
 #define SN_SCATTER_M(T, M)                                                                                           \
-    hipLaunchKernelGGL((cloud_scatter_kernel<T, M>), grd, dim3(kLanes), 0, sn::as_stream(stream),                       \
+    hipLaunchKernelGGL((cloud_scatter_kernel<T, M>), grd, dim3(kWaveLanes), 0, sn::as_stream(stream),                       \
                        static_cast<const T*>(grid), V, n0, n1, n2, P, desc, dlen, nchunks, static_cast<const int64_t*>(ws), \
                        offsets, capacity, rows, xyz, rgb16)
 #define SN_SCATTER(T)                                                     \

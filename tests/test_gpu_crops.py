@@ -85,6 +85,28 @@ def test_seams_of_chunks_and_region_tiles(hip_device, which):
     assert members > 0 or n < 64
 
 
+def test_prefix_carries_into_the_second_scan_tile(hip_device):
+    """The prefix kernel scans a region's row in tiles of 256 threads x 8 slots = 2048 chunks and carries the running total
+    from one tile to the next: one chunk more than a tile, so the prefixes of chunk 2048 and the totals hold a carry.  (Not
+    a case of the seam test above: its K = 300 regions would cost the oracle minutes at this size.)"""
+    c = _hip.crops_chunk_points()
+    tile = 256 * 8                                   # kScanThreads * kScanItems of scan.h
+    n = (tile + 1) * c + 17
+    rng = np.random.default_rng(2049)
+    pts = cc.ORIGIN + rng.random((n, 3)) * np.array([60.0, 60.0, 40.0])
+    labels = rng.choice(np.array([0.0, 2.0, 15.0, 16.0]), n)
+    x0, y0 = cc.ORIGIN[:2]
+    regions = np.array([[x0 - 1.0, y0 - 1.0, x0 + 30.0, y0 + 61.0],            # a box: the left half of the scan
+                        [x0 + 40.0, y0 + 20.0, 12.5, 0.0]])                      # a disc
+    kinds = np.array([cc.BOX, cc.DISC], dtype=np.int32)
+    crops = _crop(hip_device, pts, labels, regions, kinds)
+    offsets, src = _assert_equals_oracle(crops, pts, labels, regions, kinds, "carry")
+    assert 0.45 * n < offsets[1] < 0.55 * n
+    for k in range(2):                               # members on both sides of the seam: a dropped carry cannot pass
+        s = src[offsets[k]:offsets[k + 1]]
+        assert (s < tile * c).sum() > 1000 and (s >= tile * c).sum() > 10, f"region {k}"
+
+
 def test_all_discs_when_kinds_is_null(hip_device):
     pts, labels, regions, _ = cc.random_case(2500, 40, seed=7, mixed=False)
     crops = _crop(hip_device, pts, labels, regions, None)

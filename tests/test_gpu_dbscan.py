@@ -173,6 +173,35 @@ def test_scan_chunk_seams(hip_device, n):
     _check(_run(hip_device, P, 1.2, 4, labels, [15.0]), P, 1.2, 4, labels, [15.0])
 
 
+def test_select_prefix_carries_into_the_second_scan_tile(hip_device):
+    """The select's prefix kernel is one workgroup of 1024 threads, one chunk of 1024 points each: one chunk more than that
+    and a little, so the prefixes of chunk 1024 and n_sel hold a carry."""
+    c = _hip.points_select_chunk_points()
+    tile = 1024                                      # kScanThreads of dbscan.hip
+    n = (tile + 1) * c + 3
+    rng = np.random.default_rng(1025)
+    P = dc.ORIGIN + rng.random((n, 3)) * 50.0
+    P[rng.random(n) < 0.001, 1] = np.nan             # left out of the box
+    P[[7, n - 2], 2] = [np.inf, -np.inf]
+    labels = rng.choice(np.array([15.0, 2.0, 16.0, np.nan]), n)
+    labels[[tile * c - 1, tile * c, n - 1]] = [15.0, 16.0, 15.0]
+    keep = [15.0, 16.0]
+    want = np.nonzero(np.isin(labels, keep))[0]
+    assert (want < tile * c).sum() > 0.4 * tile * c and (want >= tile * c).sum() > 300      # selected on both sides
+    d_pts, d_lab = torch.from_numpy(P).to(hip_device), torch.from_numpy(labels).to(hip_device)
+    ws = torch.empty(_hip.points_select_ws_bytes(n) // 8, dtype=torch.int64, device=hip_device)
+    sel = torch.full((len(want) + 50,), SENTINEL, dtype=torch.int64, device=hip_device)
+    n_sel, bbox = torch.zeros(1, dtype=torch.int64, device=hip_device), torch.zeros(6, dtype=torch.float64, device=hip_device)
+    _hip.points_select(d_pts, d_lab, torch.tensor(keep, dtype=torch.float64, device=hip_device), ws, sel, n_sel, bbox,
+                       capacity=len(want) + 50)
+    assert int(n_sel) == len(want)
+    assert np.array_equal(sel[:len(want)].cpu().numpy(), want) and (sel[len(want):] == SENTINEL).all()
+    Q = P[want]
+    finite = np.where(np.isfinite(Q), Q, np.nan)
+    assert np.array_equal(bbox.cpu().numpy(), np.concatenate([np.nanmin(finite, axis=0), np.nanmax(finite, axis=0)]))
+    assert np.array_equal(bbox.cpu().numpy(), dc.finite_bbox(Q))
+
+
 def test_capacity_and_max_clusters(hip_device):
     P, eps, mp = dc.blobs_case(1)
     scan, labels = _embed(P, 11)

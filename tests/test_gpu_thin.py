@@ -119,6 +119,29 @@ def test_seams_one_tile(hip_device, idx):
     check(out, exp, [tile], [lab], tc.NONE)
 
 
+def test_prefix_carries_into_the_second_scan_tile(hip_device):
+    """The prefix kernel scans kept / lost in tiles of 256 threads x 8 slots = 2048 chunks and carries the running total
+    from one tile to the next.  One chunk more than a tile, and a tile of the batch that starts inside that chunk: its
+    offsets_out is bits_before on a prefix that holds the carry."""
+    c = _hip.thin_chunk_points()
+    tile = 256 * 8                                   # kScanThreads * kScanItems of scan.h
+    total = (tile + 1) * c + 5
+    cuts = [0, 1000, tile * c + 100, total]
+    rng = np.random.default_rng(2049)
+    packed = bc.UTM + rng.random((total, 3)) * 30.0
+    tiles = [packed[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+    u = rng.random(total)
+    us = [u[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+    thr = np.array([[0.45], [0.5], [0.55]])
+    exp = tc.expected_batch(tiles, tc.NONE, (1, 1, 1), None, thr, us)
+    src = exp["src"]
+    assert (src < tile * c).sum() > 0.4 * tile * c and (src >= tile * c + 100).sum() > 300    # kept rows on both sides
+    assert 20 < ((src >= tile * c) & (src < tile * c + 100)).sum() < 100            # ... and between the two seams
+    out = run(hip_device, tiles, None, tc.NONE, (1, 1, 1), None, thr, us=us)
+    check(out, exp, tiles, None, tc.NONE)
+    assert out["offsets"][2] > 0.4 * tile * c and out["kept"] - out["offsets"][2] > 300
+
+
 @pytest.mark.parametrize("kind", [tc.Z, tc.VOXEL])
 def test_seams_grouped(hip_device, kind):
     c = _hip.thin_chunk_points()

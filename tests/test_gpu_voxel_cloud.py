@@ -82,6 +82,41 @@ def test_chunk_seams_in_every_dtype(hip_device, mode):
             assert tuple(cloud.bad[0].cpu().tolist()) == vc.bad_counts(grid, mode), (shape, tag)
 
 
+def test_prefix_carries_into_the_second_scan_tile(hip_device):
+    """The prefix kernel scans a tile's row in tiles of 256 threads x 8 slots = 2048 chunks and carries the running total
+    from one tile to the next: a grid of 2064 chunks with live cells on both sides of cell 2048 * 1024."""
+    c = _hip.voxel_cloud_chunk_cells()
+    shape, seam = (129, 128, 128), 256 * 8 * c       # kScanThreads * kScanItems of scan.h
+    n = int(np.prod(shape))
+    assert seam + 15 * c < n
+    rng = np.random.default_rng(2064)
+    v = rng.uniform(-1.2, 1.6, n).astype(np.float32)
+    v[rng.random(n) >= 0.01] = 0.0
+    v[[seam - 1, seam, n - 1]] = [0.5, -0.25, 1.0]
+    grid = v.reshape(shape)
+    want = vc.restate(grid, "density")
+    flat = np.flatnonzero(v)
+    assert 0.008 * n < len(want) < 0.012 * n and (flat < seam).sum() > 10000 and (flat >= seam).sum() > 100
+    cloud = sna.voxel_cloud(_dev(grid, hip_device)[None], "density")
+    assert cloud.offsets.cpu().tolist() == [0, len(want)]
+    assert _same(cloud.rows, want)
+    assert tuple(cloud.bad[0].cpu().tolist()) == vc.bad_counts(grid, "density")
+
+
+def test_more_tiles_than_the_offsets_kernel_has_threads(hip_device):
+    """257 tiles: the one workgroup of the offsets kernel (256 threads) takes a second step and carries its total"""
+    shape, B = (3, 4, 5), 257
+    grids = np.stack([vc.seam_grid(shape, 10, np.float64, seed=300 + b) for b in range(B)])
+    grids[100] = 0.0                                 # an empty tile on the way
+    want = [vc.restate(g, "density") for g in grids]
+    sizes = [0 if w is None else len(w) for w in want]
+    assert sizes[256] > 0 and sum(sizes[:256]) > 256 * 20
+    cloud = sna.voxel_cloud(_dev(grids, hip_device), "density")
+    assert cloud.offsets.cpu().tolist() == np.concatenate([[0], np.cumsum(sizes)]).tolist()
+    assert _same(cloud.rows, np.concatenate([w for w in want if w is not None]))
+    assert cloud.bad.cpu().tolist() == [list(vc.bad_counts(g, "density")) for g in grids]
+
+
 def test_batch_with_an_empty_tile_in_the_middle(hip_device):
     shape = (13, 11, 9)
     first = vc.seam_grid(shape, 10, np.float64, seed=3)
