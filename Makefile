@@ -29,8 +29,10 @@ FLAGS_las_write := -ffp-contract=off
 FLAGS_voxel_cloud := -ffp-contract=off
 # thin.hip: bins with K1's fp64 rounding sequence (binning.h) and forms its uniform without a contracted multiply-add
 FLAGS_thin := -ffp-contract=off
+# voxel_classes.hip: bins with K1's fp64 rounding sequence (binning.h) and forms 255 * c for the rgb words with one rounding
+FLAGS_voxel_classes := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

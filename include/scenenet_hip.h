@@ -1290,6 +1290,78 @@ int sn_thin_scatter(const double* pts, const double* labels, const int64_t* offs
                     double* out_labels, int64_t* out_src, int32_t* out_key, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K18 -- semantic voxel grids and class colours.
+ * replaces: classes_on_voxel (utils/voxelization.py:207-241): a pandas DataFrame of (label, z, x, y),
+ *           groupby(["z", "x", "y"]).max() and a Python loop over the occupied voxels into np.zeros; and color_pointcloud
+ *           (utils/pcd_processing.py:525-574): np.unique(classes) and a Python loop over every point with
+ *           class_color[np.where(unique_classes == c)[0][0]] inside it.
+ *
+ * batch:    the ragged CSR layout of K1 and K17: offsets [B+1] i64 with offsets[0] = 0 and offsets[B] <= total; rows at or
+ *           beyond offsets[B] are neither read for a result nor written.  Empty tiles are legal.
+ * grid:     [B, nz, nx, ny] f64.  A row is binned by K1's rule, bit for bit (the same device function as sn_voxel_scatter
+ *           and sn_thin_count), with desc [B, SN_DESC_LEN(nx, ny, nz)] as sn_voxel_prepare and its siblings build it.  A row
+ *           with a NaN coordinate or outside the table on ANY axis takes no part and is counted in unbinned [B].  A
+ *           size-mode descriptor is accepted with the caveat of sn_thin_count: the padded table is used as it stands, so a
+ *           foreign row above a tile's own last edge lands in the padding cell n_a and is NOT counted in unbinned.
+ *             a voxel no binned row falls in                       +0.0 (the reference starts from np.zeros)
+ *             a voxel whose binned rows all carry NaN labels       NaN (pandas' groupby.max of an all-NaN group)
+ *             any other voxel                                      the largest label that is not NaN, by value, as its
+ *                                                                  64-bit pattern (pandas' max skips NaN); +-inf, negatives
+ *                                                                  and denormals are ordinary values; of -0.0 and +0.0 in
+ *                                                                  one voxel, +0.0 comes out
+ *           Binned or not, a row with a NaN label is counted in nan_labels [B].
+ * classes:  [total] f64.  A value is VALID iff it is integral and in 0 .. 65535 (LAS classes are bytes, SemanticKITTI's ids
+ *           16 bits; -0.0 is class 0).  present [B, SN_CLASS_WORDS] u32: bit c of tile b (bit c & 31 of word c >> 5) is set
+ *           iff some row of the tile holds the valid value c.  rank(c) = the set bits of the tile below c: the index of c in
+ *           numpy.unique of the tile's valid classes.
+ * ------------------------------------------------------------------------- */
+#define SN_CLASS_WORDS 2048
+#define SN_VOXEL_CLASSES_NO_SKIP 1
+
+/* Rows per workgroup of sn_voxel_classes (1024) and of sn_class_census / sn_class_paint (8192): host only -- they let a
+ * test put its sizes on the seams. */
+int sn_voxel_classes_chunk_points(void);
+int sn_class_chunk_points(void);
+
+/* The class grid of every tile.  Three launches on `stream` and no memset node: one that zeroes the grid and the counters,
+ * one pass over the rows that reduces each row's order-preserving 64-bit key into the grid's own cell by integer atomic max (sent only
+ * where a plain load of the cell shows less; flags = SN_VOXEL_CLASSES_NO_SKIP sends it always -- same result, for timing),
+ * then one pass that decodes the grid in place.  unbinned and nan_labels are integer atomic sums.  Integer maxima and sums:
+ * the result does not depend on scheduling.  No allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null pts / labels / offsets / desc / grid / unbinned / nan_labels, total <= 0, B <= 0, an extent
+ * <= 0, unknown flags, a pointer that is not 8-byte aligned;  SN_ERR_UNSUPPORTED: total > 2^33, B > 65536, edge tables
+ * (nx + ny + nz + 3 doubles) beyond 64 KiB of LDS, nx * ny * nz >= 2^31.  All checked before any launch. */
+int sn_voxel_classes(const double* pts, const double* labels, const int64_t* offsets, int64_t total, int B, const double* desc,
+                     int nx, int ny, int nz, int flags, double* grid, int64_t* unbinned, int64_t* nan_labels,
+                     sn_stream_t stream);
+
+/* present [B, SN_CLASS_WORDS] and bad [B] i64 (the rows of each tile that are not valid: NaN, fractional, negative, above
+ * 65535).  Two launches and no memset node (present, bad <- 0; the rows): every workgroup builds the bitmap of its rows in LDS and merges it with 32-bit
+ * atomic OR; bad is an integer atomic sum.  No allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null classes / offsets / present / bad, total <= 0, B <= 0, classes / offsets / bad not 8-byte or
+ * present not 4-byte aligned;  SN_ERR_UNSUPPORTED: total > 2^33, B > 65536. */
+int sn_class_census(const double* classes, const int64_t* offsets, int64_t total, int B, uint32_t* present, int64_t* bad,
+                    sn_stream_t stream);
+
+/* Called with the same batch and the `present` that sn_class_census left.  table [T,3] f64 on the DEVICE.
+ *   colors [total,3] f64 (nullable): row i = the 64-bit patterns of table[rank(classes[i])]
+ *   rgb    [total,3] u16 (nullable): clamp(rint(255 * c), 0, 255) * 257 of that row's channels, the product rounded once
+ *          (K16's rule; NaN gives 0).  At least one of colors and rgb is given.
+ *   A row whose rank is >= T is counted in short_table [B] i64; it and a row that is not valid get a NaN row in colors and
+ *   zeros in rgb (the reference raises IndexError for both).
+ *   n_unique [B] i64: the tile's number of valid classes.  unique [B, U_max] f64 (nullable): the first min(n_unique, U_max)
+ *   of them in ascending order -- numpy.unique; the rest of the row is NOT touched.
+ * Two launches (one workgroup per tile: n_unique, unique, short_table <- 0; then the rows); no allocation, no
+ * synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null classes / offsets / present / table / n_unique / short_table, neither colors nor rgb, total
+ * <= 0, B <= 0, T <= 0, unique with U_max <= 0, a misaligned pointer (present 4 bytes, rgb 2, the others 8);
+ * SN_ERR_UNSUPPORTED: as sn_class_census. */
+int sn_class_paint(const double* classes, const int64_t* offsets, int64_t total, int B, const uint32_t* present,
+                   const double* table, int T, double* colors, uint16_t* rgb, double* unique, int U_max, int64_t* n_unique,
+                   int64_t* short_table, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

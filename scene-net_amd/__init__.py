@@ -34,6 +34,8 @@ from .voxel_cloud import (VoxelCloud, jet_ranges, plot_quantile_uncertainty, plo
                           write_voxel_cloud_las)
 from .thin import (ThinnedPoints, ThinPoints, downsampling, downsampling_relative_height, height_thresholds,
                    philox_uniforms, thin_points, uniform_thresholds)
+from .voxel_classes import (ClassColors, VoxelClasses, class_colors, classes_on_voxel, color_pointcloud,
+                            random_class_colors, voxel_classes)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss, GENEO_Loss,
                          GENEO_Tversky_Loss, TverskyLoss, WeightedMSE)
 
@@ -51,6 +53,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "VoxelCloud", "voxel_cloud", "plot_voxelgrid", "plot_quantile_uncertainty", "jet_ranges", "write_voxel_cloud_las",
            "ThinnedPoints", "ThinPoints", "thin_points", "downsampling", "downsampling_relative_height", "height_thresholds",
            "uniform_thresholds", "philox_uniforms",
+           "VoxelClasses", "ClassColors", "voxel_classes", "classes_on_voxel", "class_colors", "color_pointcloud",
+           "random_class_colors",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE"]

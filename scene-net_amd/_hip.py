@@ -141,6 +141,11 @@ SYMBOLS = {
                               _P]),
     "sn_thin_scatter": (c_int, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t,
                                 ctypes.c_int64, _P, _P, _P, _P, _P]),
+    "sn_voxel_classes_chunk_points": (c_int, []),
+    "sn_class_chunk_points": (c_int, []),
+    "sn_voxel_classes": (c_int, [_P, _P, _P, ctypes.c_int64, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sn_class_census": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
+    "sn_class_paint": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -158,6 +163,7 @@ SN_DBSCAN_NSTAT, SN_DBSCAN_LAUNCHES = 3, 8
 SN_KITTI_MAX_LUT, SN_KITTI_MAX_HIST = 65536, 1024
 SN_CLOUD_DENSITY, SN_CLOUD_RANGES, SN_CLOUD_MAX_R = 0, 1, 32
 SN_THIN_GROUP_NONE, SN_THIN_GROUP_Z, SN_THIN_GROUP_VOXEL = 0, 1, 2
+SN_CLASS_WORDS, SN_VOXEL_CLASSES_NO_SKIP = 2048, 1
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -1881,3 +1887,80 @@ def thin_scatter(pts: torch.Tensor, labels: Optional[torch.Tensor], offsets: tor
                                 _ptr(out_pts, torch.float64, "out_pts"), _ptr(out_labels, torch.float64, "out_labels"),
                                 _ptr(out_src, torch.int64, "out_src"), _ptr(out_key, torch.int32, "out_key"), _stream())
     _check(rc, "sn_thin_scatter")
+
+
+# --------------------------------------------------------------------------- #
+def voxel_classes_chunk_points() -> int:
+    """sn_voxel_classes_chunk_points: rows per workgroup of the class-grid kernel (host only)."""
+    return int(load().sn_voxel_classes_chunk_points())
+
+
+def class_chunk_points() -> int:
+    """sn_class_chunk_points: rows per workgroup of the class census and paint kernels (host only)."""
+    return int(load().sn_class_chunk_points())
+
+
+@_on_tensor_device
+def voxel_classes(pts: torch.Tensor, labels: torch.Tensor, offsets: torch.Tensor, desc: torch.Tensor, n_xyz: Sequence[int],
+                  grid: torch.Tensor, unbinned: torch.Tensor, nan_labels: torch.Tensor, skip: bool = True) -> None:
+    """sn_voxel_classes: pts [total,3] f64, labels [total] f64, offsets [B+1] i64, desc [B, desc_len] -> grid [B,nz,nx,ny] f64
+    (any shape of B * nz * nx * ny elements), unbinned [B] i64, nan_labels [B] i64, all caller-owned.  skip=False sends
+    every row's atomic (same result; for timing).  No allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [total, 3] (got {tuple(pts.shape)})")
+    total, B = int(pts.shape[0]), int(offsets.numel()) - 1
+    nx, ny, nz = (int(v) for v in n_xyz)
+    if labels.numel() != total:
+        raise HipLibraryError("labels and pts disagree in length")
+    if tuple(desc.shape) != (B, desc_len(nx, ny, nz)):
+        raise HipLibraryError(f"desc must be [B, desc_len(nx, ny, nz)] = [{B}, {desc_len(nx, ny, nz)}] "
+                              f"(got {tuple(desc.shape)})")
+    if grid.numel() != B * nx * ny * nz or unbinned.numel() != B or nan_labels.numel() != B:
+        raise HipLibraryError("grid must hold B * nz * nx * ny cells, unbinned and nan_labels B entries")
+    rc = load().sn_voxel_classes(_ptr(pts, torch.float64, "pts"), _ptr(labels, torch.float64, "labels"),
+                                 _ptr(offsets, torch.int64, "offsets"), total, B, _ptr(desc, torch.float64, "desc"), nx, ny,
+                                 nz, 0 if skip else SN_VOXEL_CLASSES_NO_SKIP, _ptr(grid, torch.float64, "grid"),
+                                 _ptr(unbinned, torch.int64, "unbinned"), _ptr(nan_labels, torch.int64, "nan_labels"),
+                                 _stream())
+    _check(rc, "sn_voxel_classes")
+
+
+@_on_tensor_device
+def class_census(classes: torch.Tensor, offsets: torch.Tensor, present: torch.Tensor, bad: torch.Tensor) -> None:
+    """sn_class_census: classes [total] f64, offsets [B+1] i64 -> present [B, SN_CLASS_WORDS] i32 (the u32 words' bits), bad
+    [B] i64, caller-owned.  No allocation, no synchronisation."""
+    total, B = int(classes.numel()), int(offsets.numel()) - 1
+    if present.numel() != B * SN_CLASS_WORDS or bad.numel() != B:
+        raise HipLibraryError(f"present must be [B, {SN_CLASS_WORDS}] and bad [B] for B = {B}")
+    rc = load().sn_class_census(_ptr(classes, torch.float64, "classes"), _ptr(offsets, torch.int64, "offsets"), total, B,
+                                _ptr(present, torch.int32, "present"), _ptr(bad, torch.int64, "bad"), _stream())
+    _check(rc, "sn_class_census")
+
+
+@_on_tensor_device
+def class_paint(classes: torch.Tensor, offsets: torch.Tensor, present: torch.Tensor, table: torch.Tensor,
+                colors: Optional[torch.Tensor], rgb: Optional[torch.Tensor], unique: Optional[torch.Tensor],
+                n_unique: torch.Tensor, short_table: torch.Tensor) -> None:
+    """sn_class_paint behind class_census: table [T,3] f64 on the device -> colors [total,3] f64 and / or rgb [total,3]
+    u16 (int16 storage serves), unique [B, U_max] f64 | None, n_unique [B] i64, short_table [B] i64, caller-owned; the
+    outputs may be longer than the batch, rows beyond it are left as they are.  No allocation, no synchronisation."""
+    total, B = int(classes.numel()), int(offsets.numel()) - 1
+    if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1:
+        raise HipLibraryError(f"table must be [T, 3] with T >= 1 (got {tuple(table.shape)})")
+    if present.numel() != B * SN_CLASS_WORDS or n_unique.numel() != B or short_table.numel() != B:
+        raise HipLibraryError(f"present must be [B, {SN_CLASS_WORDS}], n_unique and short_table [B] for B = {B}")
+    if colors is None and rgb is None:
+        raise HipLibraryError("one of colors and rgb is needed")
+    if any(t is not None and t.numel() < 3 * total for t in (colors, rgb)):
+        raise HipLibraryError("colors / rgb hold fewer than total rows")
+    U_max = 0
+    if unique is not None:
+        if unique.dim() != 2 or unique.shape[0] != B or unique.shape[1] < 1:
+            raise HipLibraryError(f"unique must be [B, U_max] with U_max >= 1 (got {tuple(unique.shape)})")
+        U_max = int(unique.shape[1])
+    rc = load().sn_class_paint(_ptr(classes, torch.float64, "classes"), _ptr(offsets, torch.int64, "offsets"), total, B,
+                               _ptr(present, torch.int32, "present"), _ptr(table, torch.float64, "table"),
+                               int(table.shape[0]), _ptr(colors, torch.float64, "colors"), _u16_ptr(rgb, "rgb"),
+                               _ptr(unique, torch.float64, "unique"), U_max, _ptr(n_unique, torch.int64, "n_unique"),
+                               _ptr(short_table, torch.int64, "short_table"), _stream())
+    _check(rc, "sn_class_paint")
