@@ -58,6 +58,19 @@
 //     prologue allows skipping (can_skip, workgroup-uniform) only if all 16 entries of scale, lamsc and lamhi are finite
 //     (scale not negative) and sn_set_option("conv_i8z_dense") is 0; otherwise every round runs, NaN / inf propagate.
 //   sn_conv_i8z_round_counts: rounds run / skipped, summed per workgroup in LDS and added once at its end.
+//
+// THE LEAN TICKET (round 7, head-only form).  [measured, tools/micro/issue_model.hip s] a scalar instruction costs a SIMD 3.6
+// cycles at three waves per SIMD (the CU's one scalar unit serves four SIMDs) and only part of the other waves' vector issue
+// hides beside it; a ticket of round 6 whose two rounds were empty still executed ~325 scalar and ~135 vector instructions, and
+// on an all-zero batch the part of a ticket behind its passes was 52 % of a wave's time.  So a ticket forms its verdict FIRST,
+// from one union window over all its rounds (rows lx .. lx + kH kR + 7; the mask a constant selected by lx & 3 and shifted by
+// bytes, not rebuilt with shifts and ors), and when that is empty it issues nothing of the round set-up: the read[] report
+// (behind the wait for the mask read, as before), one scalar row address from the job's base out + b V -- formed when the job
+// changes, as is x + b V for the LDS-DMA -- and the stores of the constant + 0.0 (relu_tanh(+ 0.0) is + 0.0: see relu_tanh),
+// both rows in one store of two values per lane where they are contiguous (one y tile spans Y), else two stores from the one
+// base; under head & 1 the load-add-activate of zero_round1 / zero_round2 stays.  The per-round verdicts, the table reads and
+// the ring addresses are formed only for a ticket that runs a round.  The activations form (kAct) keeps the round-6 ticket:
+// see kLean in the kernel.
 
 constexpr int kZTX = 8;                        // output x-rows per column
 constexpr int kZRows = kZTX + 8;               // halo rows per plane
@@ -307,6 +320,21 @@ __device__ __forceinline__ void zero_round2(const SH& s, const TileCoord& c, int
     }
 }
 
+// The row bits of a window of kRows + 8 halo rows that starts at row r = 4 a + c, in the row masks' layout (byte xr, bit q =
+// row 4 xr + q): a constant selected by c, moved up a bytes (rows past 15 fall off the top, as they do not exist).  Scalar;
+// the callers pass c in a form that shows which values it can take (rebuilt with shifts and ors per round it was ~10 scalar
+// instructions).
+constexpr uint32_t zrow_bits(uint32_t w) {
+    return (w & 0xfu) | ((w & 0xf0u) << 4) | ((w & 0xf00u) << 8) | ((w & 0xf000u) << 12);
+}
+template <int kRows>
+__device__ __forceinline__ uint32_t zwindow_mask(int c, int a) {
+    constexpr uint32_t W = (1u << (8 + kRows)) - 1u;
+    static_assert(kRows == 1 || kRows == 2, "a window of 9 or 10 rows: W << 3 stays inside 16 bits");
+    const uint32_t m = c == 0 ? zrow_bits(W) : c == 1 ? zrow_bits(W << 1) : c == 2 ? zrow_bits(W << 2) : zrow_bits(W << 3);
+    return m << (8 * a);
+}
+
 // LDS counter add by ONE lane, as the instruction it is: hipcc's atomic optimiser turns `if (lane == 0) atomic_add` into a
 // cross-lane aggregation (mbcnt, bcnt, a second exec dance: ~12 instructions per signal, four signals per ticket)
 // kTag names the hand-over in the ISA (a comment inside the asm block: `; @zw:add<kTag>`), for tools/zwalk_handover_audit.py:
@@ -336,6 +364,13 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
                                                                 OT* __restrict__ act_arg, OT* __restrict__ out) {
     if (!zs.gate.pass()) return;
     OT* const act = kAct ? act_arg : nullptr;
+    // kLean (round 7): the head-only form takes the ticket's verdict first and stores an all-empty ticket's rows from one row
+    // address (THE TICKET'S VERDICT FIRST, below).  The activations form keeps the round-6 ticket as it was: with the lean
+    // ticket's code in, the (1, 2, 12) activations instantiation stored a stray + 0.0 into single activations of kernel 13 on
+    // some launches ([measured] tests/test_gpu_conv_zwalk_skip.py::test_half_occupancy_skips_nothing, also with
+    // conv_i8z_dense = 1, i.e. with none of the new code executed: a sensitivity of the generated code that is not understood),
+    // so nothing about that form's code is changed.
+    constexpr bool kLean = !kAct;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr int kNT = 64 * kW;              // threads
     constexpr int kTPS = kZTX / (kH * kR);    // tickets per slot: 8 or 4
@@ -449,21 +484,29 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     // the job a plane / an output belongs to: (b, x0, y0, zs) in scalar registers, re-read from the table only when the
     // job index changes (a table read per ticket was an exposed LDS round trip)
     struct JobRegs { int k, b, x0, y0, zs; };
-    auto job_fetch = [&](JobRegs& jr, int k) {
-        if (k != jr.k) {
-            const int4 jb = jobtab[k];
-            jr.b = __builtin_amdgcn_readfirstlane(jb.x); jr.x0 = __builtin_amdgcn_readfirstlane(jb.y);
-            jr.y0 = __builtin_amdgcn_readfirstlane(jb.z); jr.zs = __builtin_amdgcn_readfirstlane(jb.w);
-            jr.k = k;
-        }
+    auto job_fetch = [&](JobRegs& jr, int k) -> bool {   // (true: the job changed)
+        if (k == jr.k) return false;
+        const int4 jb = jobtab[k];
+        jr.b = __builtin_amdgcn_readfirstlane(jb.x); jr.x0 = __builtin_amdgcn_readfirstlane(jb.y);
+        jr.y0 = __builtin_amdgcn_readfirstlane(jb.z); jr.zs = __builtin_amdgcn_readfirstlane(jb.w);
+        jr.k = k;
+        return true;
     };
     JobRegs jd{-1, 0, 0, 0, 0}, jr{-1, 0, 0, 0, 0};
+    // kLean: the jobs' tile bases x + b V and out + b V are 64-bit scalars formed when the job changes, not per pass and per
+    // round (round 7: the product b V was formed three times per ticket); everything below adds 32-bit offsets (the host
+    // checks Z X Y < 2^31)
+    const uint8_t* xb = x;
+    OT* ob = nullptr;
 
     // ---- LDS-DMA of four raw rows (pass xr) of plane u: 24 lanes x 16 B, rows contiguous in the ring slot
     auto dma_pass = [&](int u, int xr, int ln) {
         const int dl_row = (ln * 43) >> 8, dl_i = ln - dl_row * kRowPieces;   // ln / 6, ln % 6 for ln < 24 (the lanes that take part)
         const int k = (int)__umulhi((unsigned)u, zs.pl_magic), p = u - k * zs.PL;
-        job_fetch(jd, k);
+        const bool new_job = job_fetch(jd, k);
+        if constexpr (kLean) {
+            if (new_job) xb = x + (size_t)jd.b * V;
+        }
         const int gz = jd.zs - 4 + p;
         const int gx = jd.x0 - 4 + 4 * xr + dl_row, gy = jd.y0 - PYA + 16 * dl_i;
         const bool ok = (unsigned)gz < (unsigned)zs.Z && (unsigned)gx < (unsigned)zs.X && (unsigned)gy < (unsigned)zs.Y;
@@ -471,7 +514,8 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         const uint32_t lds_uni = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)dst);
         // tile base (scalar, 64-bit) + a 32-bit offset inside the tile (the host checks Z X Y < 2^31); pieces outside the grid
         // are fetched from the 16 zero bytes of the caller's blob (a kernel argument: no GOT load for a zero block)
-        const uint8_t* src = ok ? x + (size_t)jd.b * V + (unsigned)((gz * zs.X + gx) * zs.Y + gy) : prep + kPrepZero;
+        const uint8_t* const tile = kLean ? xb : x + (size_t)jd.b * V;
+        const uint8_t* src = ok ? tile + (unsigned)((gz * zs.X + gx) * zs.Y + gy) : prep + kPrepZero;
         if (ln < 4 * kRowPieces) {
             uint32_t m0_saved;
             asm volatile("; @zw:dma\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
@@ -607,10 +651,13 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const int s = t >> kTShift, tk = t & (kTPS - 1);
-        // the round's table rows are requested here, a dependency check and two passes ahead of their use (tables, not rings:
-        // nothing of the hand-over protocol; requested at the set-up itself their latency ate what the table saves)
-        const int4 LT = ltab[ln];
-        const int4 ST = *reinterpret_cast<const int4*>(reinterpret_cast<const uint8_t*>(stab) + ((s - kZD) & 15) * 64 + (ln & 0x30));
+        // !kLean: the round's table rows are requested here, a dependency check and two passes ahead of their use (tables, not
+        // rings: nothing of the hand-over protocol; requested at the set-up itself their latency ate what the table saves)
+        int4 LT, ST;
+        if constexpr (!kLean) {
+            LT = ltab[ln];
+            ST = *reinterpret_cast<const int4*>(reinterpret_cast<const uint8_t*>(stab) + ((s - kZD) & 15) * 64 + (ln & 0x30));
+        }
         const bool pass_ticket = kTPS <= 4 || (tk & 1) == 0;      // this ticket carries LDS-DMA / fold passes
         const int xr0 = kTPS == 8 ? tk >> 1 : tk;                 // ... pass xr0 of the plane
         const int sd = s + kZDD;
@@ -704,14 +751,81 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             continue;
         }
         const unsigned long long tz3 = SN_ZNOW();
-        job_fetch(jr, kr);
-        TileCoord c;
-        c.b = jr.b; c.x0 = jr.x0; c.y0 = jr.y0; c.z0 = jr.zs + o;
+        const bool new_job = job_fetch(jr, kr);
+        if constexpr (kLean) {
+            if (new_job && out) ob = out + (size_t)jr.b * V;
+        }
+        const int gz = jr.zs + o;
         const int lx = kH * kR * tk;   // the ticket's first x-row
-        if (c.z0 >= zs.Z || c.x0 + lx >= zs.X) {   // (a last segment shorter than LZ; x-rows past the grid)
+        int rows_left = 0, nvalid = 0;   // rounds of this ticket that lie inside the grid (x-rows past X end the ticket early)
+        if (gz >= zs.Z || jr.x0 + lx >= zs.X) {   // (a last segment shorter than LZ; x-rows past the grid)
             asm volatile("; @zw:wait3\n\ts_waitcnt lgkmcnt(0)" ::: "memory");   // (the mask read: nothing else was read)
             lds_add_lane0<3>(&cnt[16 + (s & 15)], 1, lane);
             continue;
+        }
+        if constexpr (kLean) {
+            rows_left = zs.X - (jr.x0 + lx);
+            nvalid = rows_left >= kH * kR ? kR : (rows_left + kH - 1) / kH;
+        }
+        // THE TICKET'S VERDICT FIRST (round 7): one window over all its rounds -- rows lx .. lx + kH kR + 7 of the nine planes,
+        // the union of the rounds' windows -- decides whether anything of the round set-up below is needed.  On the C2 batch
+        // 72 % of the rounds are empty and most empty rounds share their ticket with another: such a ticket pays the report,
+        // one row address and its stores, nothing else.
+        if (kLean && can_skip) {
+            const uint32_t ub = zwindow_mask<kH * kR>(kH * kR == 2 ? (tk & 1) * 2 : (tk & 3), kH * kR == 2 ? tk >> 1 : tk >> 2);
+            if (((uint32_t)__builtin_amdgcn_ballot_w64((rmask & ub) != 0u) & 0x1ffu) == 0u) {
+                // every round of the ticket is empty.  The read[] report stays where an empty round's was (HAND-OVER 3): the
+                // mask read has returned (the verdict needed it), nothing else was read.
+                asm volatile("; @zw:wait3\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_add_lane0<3>(&cnt[16 + (s & 15)], 1, lane);
+                n_skip += nvalid;
+                // what the rounds would store for all-zero accumulators (zero_round1 / zero_round2 above).  Under head & 1 (load,
+                // add, activate) that is those functions' own; without head & 1 the value is relu_tanh(+ 0.0) or + 0.0 itself --
+                // both are + 0.0 bits (relu_tanh: 0 < v fails, v != v fails: the constant 0.0f) -- and is stored as that constant:
+                // one row address per ticket, no evaluation per round.
+                if (ob && (zs.head & 1)) {
+                    TileCoord c;
+                    c.b = 0; c.x0 = jr.x0; c.y0 = jr.y0; c.z0 = gz;   // (b: in the base)
+                    const int n = ln & 15, q = ln >> 4;
+#pragma unroll 1
+                    for (int rr = 0; rr < nvalid; ++rr) {
+                        if constexpr (kH == 2) zero_round2<OT>(zs, c, lx + rr * kH, n, q, act, ob, V);
+                        else zero_round1<OT>(zs, c, lx + rr * kH, n, q, 4 * n + q, act, ob, V);
+                    }
+                }
+                if (ob && !(zs.head & 1)) {
+                    OT* const row = ob + (unsigned)((gz * zs.X + jr.x0 + lx) * zs.Y);   // (scalar; y = 0 of the ticket's first row)
+                    float z0 = 0.0f;
+                    asm volatile("" : "+v"(z0));   // (made here: as a loop invariant the constant pair was kept in registers and spilled)
+                    const OT zero = (OT)z0;
+                    if (kH * kR == 2 && rows_left >= 2 && zs.nyt == 1) {
+                        // both rows lie in the grid and one y tile spans Y: 2 Y consecutive values, two per lane
+                        if (ln < zs.Y) {
+                            OT* const o2 = row + 2u * (unsigned)ln;
+                            if constexpr (sizeof(OT) == 4) *reinterpret_cast<float2*>(o2) = make_float2(zero, zero);
+                            else *reinterpret_cast<double2*>(o2) = make_double2(zero, zero);
+                        }
+                    } else {
+                        const int gy = jr.y0 + ln;
+                        if (gy < zs.Y) {
+                            row[(unsigned)gy] = zero;
+                            if (kH * kR == 2 && rows_left >= 2) row[(unsigned)(zs.Y + gy)] = zero;
+                        }
+                    }
+                }
+                SN_ZT(6, tz0);
+                continue;
+            }
+        }
+        // ---- the round set-up: only for a ticket that runs a round (or may not skip)
+        TileCoord c;
+        c.b = kLean ? 0 : jr.b; c.x0 = jr.x0; c.y0 = jr.y0; c.z0 = gz;   // (kLean: b is in the base ob)
+        OT* const oq = kLean ? ob : out;
+        // kLean: the rounds' table rows (tables, not rings: nothing of the hand-over protocol); their latency hides behind the
+        // scalar part of the set-up and the per-round masks
+        if constexpr (kLean) {
+            LT = ltab[ln];
+            ST = *reinterpret_cast<const int4*>(reinterpret_cast<const uint8_t*>(stab) + ((s - kZD) & 15) * 64 + (ln & 0x30));
         }
         // (the rounds' per-lane constants, likewise from an opaque lane id: see the top of the ticket)
         const int lr = ln;
@@ -780,16 +894,23 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
 #pragma unroll
             for (int r = 0; r < 4; ++r) X[r][3] = (int)ov[r];
         };
-        // rounds of this ticket that lie inside the grid (x-rows past X end the ticket early)
-        const int rows_left = zs.X - (c.x0 + lx);
-        const int nvalid = rows_left >= kH * kR ? kR : (rows_left + kH - 1) / kH;
+        if constexpr (!kLean) {
+            rows_left = zs.X - (c.x0 + lx);
+            nvalid = rows_left >= kH * kR ? kR : (rows_left + kH - 1) / kH;
+        }
         // which of the ticket's rounds have a set voxel in their window (wave-uniform): rows lx + rr kH .. + kH + 7 of the
-        // nine planes, as bits of the masks' layout (byte xr, bit q)
+        // nine planes, as bits of the masks' layout (byte xr, bit q).  (kR = 1: the ticket's verdict above was the round's.)
         uint32_t hits[kR];   // lanes 0..8 with a row bit inside the window of round rr (scalar)
 #pragma unroll
         for (int rr = 0; rr < kR; ++rr) {
-            const uint32_t w = ((1u << (8 + kH)) - 1u) << (lx + rr * kH);
-            uint32_t wb = (w & 0xfu) | ((w & 0xf0u) << 4) | ((w & 0xf00u) << 8) | ((w & 0xf000u) << 12);
+            if (kLean && kR == 1) { hits[rr] = 1u; continue; }
+            uint32_t wb;
+            if constexpr (kLean) {
+                wb = zwindow_mask<kH>((tk & 1) * 2 + rr, tk >> 1);   // (kH = 1, kR = 2: row 2 tk + rr)
+            } else {
+                const uint32_t w = ((1u << (8 + kH)) - 1u) << (lx + rr * kH);
+                wb = (w & 0xfu) | ((w & 0xf0u) << 4) | ((w & 0xf00u) << 8) | ((w & 0xf000u) << 12);
+            }
             asm("" : "+s"(wb));   // (one scalar operand: v_and + v_cmp per round)
             hits[rr] = can_skip ? ((uint32_t)__builtin_amdgcn_ballot_w64((rmask & wb) != 0u) & 0x1ffu) : 1u;
         }
@@ -806,8 +927,8 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
                     asm volatile("; @zw:wait3\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
                     lds_add_lane0<3>(&cnt[16 + (s & 15)], 1, lane);
                 }
-                if constexpr (kH == 2) zero_round2<OT>(zs, c, lx + rr * kH, n, q, act, out, V);
-                else zero_round1<OT>(zs, c, lx + rr * kH, n, q, LT.z, act, out, V);
+                if constexpr (kH == 2) zero_round2<OT>(zs, c, lx + rr * kH, n, q, act, oq, V);
+                else zero_round1<OT>(zs, c, lx + rr * kH, n, q, LT.z, act, oq, V);
                 ++n_skip;
                 yqA += kH * kZYqRow; yqB += kH * kZYqRow; yq8 += kH * kZYqRow;
                 ycA += kH * kZYcRow; ycB += kH * kZYcRow; yc8 += kH * kZYcRow;
@@ -926,8 +1047,13 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             }
             SN_ZT(4, tz4);
             const unsigned long long tz5 = SN_ZNOW();
-            if constexpr (kH == 2) finish_round<OT>(zs, c, 0, lx + rr * kH, n, q, acc, scale, lamsc, lamhi, act, out, V);
-            else finish_round1<OT>(zs, c, lx + rr * kH, n, q, LT.z, LT.w, acc, scale, lamsc, lamhi, act, out, V);
+            if constexpr (kH == 2 && kLean) {
+                // (n and q again from the lane id: kept live through the MFMA steps of this 256-register shape they were spilled)
+                int le = lr;
+                asm volatile("" : "+v"(le));
+                finish_round<OT>(zs, c, 0, lx + rr * kH, le & 15, le >> 4, acc, scale, lamsc, lamhi, act, oq, V);
+            } else if constexpr (kH == 2) finish_round<OT>(zs, c, 0, lx + rr * kH, n, q, acc, scale, lamsc, lamhi, act, oq, V);
+            else finish_round1<OT>(zs, c, lx + rr * kH, n, q, LT.z, LT.w, acc, scale, lamsc, lamhi, act, oq, V);
             SN_ZT(5, tz5);
             yqA += kH * kZYqRow; yqB += kH * kZYqRow; yq8 += kH * kZYqRow;
             ycA += kH * kZYcRow; ycB += kH * kZYcRow; yc8 += kH * kZYcRow;

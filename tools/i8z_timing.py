@@ -2,7 +2,8 @@
 """Debug only: per-wave phase cycles of the z-walk kernel (conv_occ_i8z_kernel) at C2 from the s_memtime stamps of a
 timing build:
     make -B EXTRA=-DSN_CONV_TIMING OUT=build/timing OBJDIR=build/obj_timing
-    SN_HIP_LIB=build/timing/libscenenet_hip.so python tools/i8z_timing.py"""
+    SN_HIP_LIB=build/timing/libscenenet_hip.so python tools/i8z_timing.py [--zero]
+--zero: an all-zero batch of the same shape (no round runs: what the tickets' bookkeeping alone costs)"""
 import ctypes, os, sys
 import numpy as np
 import torch
@@ -18,6 +19,8 @@ model = model.to(dev)
 bank, lam = model.compute_bank(dev), model.effective_lambdas(dev)
 tiles = [synthetic_tile(i, 100_000)[0] for i in range(32)]
 occ = sna.voxelize_batch(sna.PointBatch.from_tiles(tiles, device=dev), (64,) * 3, occ_dtype=torch.bool).occ
+if "--zero" in sys.argv:   # the all-zero batch: every ticket is an empty one
+    occ = torch.zeros_like(occ)
 prep = _hip.conv_bank_prep(bank)
 for _ in range(200):
     _hip.conv_bank(occ, bank, lam, want_act=False, want_out=True, prep=prep)

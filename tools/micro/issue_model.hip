@@ -2,6 +2,7 @@
 // 5.0 VALU per v_mfma_i32_16x16x64_i8, three waves per SIMD, matrix pipe 42 % busy): is the launch bound by the SIMD's
 // issue (then only fewer instructions help) or by how the waves' phases line up (then the schedule helps)?
 //   hipcc --offload-arch=gfx950 -O3 tools/micro/issue_model.hip -o /tmp/issue_model && /tmp/issue_model
+//   (argument `l`: the LDS reads of (2) below; argument `s`: the scalar instructions of (3))
 // One workgroup per CU (100 KB of LDS), W waves per SIMD.  A wave's stream per trip: 48 MFMAs on 12 independent accumulators
 // and 48 * NV v_alignbyte on 8 independent chains, laid out
 //   mode 0  fine:   [1 MFMA, NV VALU] x 48
@@ -194,6 +195,113 @@ void sweep_lds() {
     run_lds<W, 4, 8, false>("[4 ds_read_b64] alone");
 }
 
+// ---- (3) scalar ALU instructions: alone, beside the MFMAs, beside VALU of the same and of other waves.  The question behind
+// the z-walk's EMPTY ticket (csrc/conv_i8z.inc: ~325 scalar against ~135 vector instructions): a CU's four SIMDs share one
+// scalar unit -- what does a scalar instruction cost a SIMD, and does it hide beside the vector issue of the SIMD's other waves?
+// A wave's stream per trip: 48 slots of [kMfma: 1 MFMA] [NV v_alignbyte] [NS scalar], the scalar ones alternately s_add_u32
+// (writes SCC) and s_mul_i32 on 8 independent chains.  Reported: cycles per slot of the SIMD (calibrated by the MFMA-only
+// stream of the same W: 16 cycles per MFMA) and, for the rows that have them, per scalar instruction of the SIMD.
+template <int W, int NS, int NV, bool kMfma>
+__global__ __launch_bounds__(W * 256) void scalar_kernel(int iters, int* out, long long* stamps, unsigned seed) {
+    extern __shared__ int lds[];
+    i32x4 acc[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] = i32x4{0, 0, 0, 0};
+    const unsigned s = mixu(threadIdx.x * 977u + blockIdx.x * 131u + 1u);
+    i32x4 a[3], b[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a[i] = i32x4{(int)mixu(s + i), (int)mixu(s + 11 + i), (int)mixu(s + 22 + i), (int)mixu(s + 33 + i)};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b[i] = i32x4{(int)mixu(s + 4 + i), (int)mixu(s + 55 + i), (int)mixu(s + 66 + i), (int)mixu(s + 77 + i)};
+    unsigned x[8], y[8], sc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        x[i] = mixu(s + 100 + i); y[i] = mixu(s + 200 + i);
+        sc[i] = __builtin_amdgcn_readfirstlane(mixu(seed + blockIdx.x * 8 + i));
+    }
+    const unsigned sk = __builtin_amdgcn_readfirstlane(mixu(seed + 77u) | 1u);
+    if (threadIdx.x == 0) lds[0] = (int)s;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    const long long t0 = (long long)__builtin_readcyclecounter();
+    for (int it = 0; it < iters; ++it) {
+        int rot = 0;
+#pragma unroll
+        for (int m = 0; m < 48; ++m) {
+            if constexpr (kMfma) acc[m % 12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[m % 3], b[(m / 3) & 3], acc[m % 12], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NV > 0) valu_block<NV>(x, y, NV, rot);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const int j = (m * NS + k) & 7;
+                if (k & 1) asm volatile("s_mul_i32 %0, %0, %1" : "+s"(sc[j]) : "s"(sk));
+                else asm volatile("s_add_u32 %0, %0, %1" : "+s"(sc[j]) : "s"(sk) : "scc");
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const long long t1 = (long long)__builtin_readcyclecounter();
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) t += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t += (int)x[i] + (int)sc[i];
+    if (t == 0x7fffffff) out[0] = t;
+    if ((threadIdx.x & 63) == 0) stamps[blockIdx.x * (W * 4) + wave] = t1 - t0;
+}
+
+template <int W, int NS, int NV, bool kMfma>
+double run_scalar(const char* what, double base_ms) {
+    int* d = nullptr;
+    long long* st = nullptr;
+    if (hipMalloc(&d, 4) != hipSuccess || hipMalloc(&st, 256 * W * 4 * 8) != hipSuccess) return 0;
+    const int iters = 400;
+    auto k = scalar_kernel<W, NS, NV, kMfma>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    for (int i = 0; i < 3; ++i) k<<<256, W * 256, 100 * 1024>>>(iters, d, st, 12345u);
+    (void)hipDeviceSynchronize();
+    const int reps = 5;
+    (void)hipEventRecord(e0);
+    for (int i = 0; i < reps; ++i) k<<<256, W * 256, 100 * 1024>>>(iters, d, st, 12345u);
+    (void)hipEventRecord(e1);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    ms /= reps;
+    // the MFMA-only stream of the same W takes 16 cycles per slot of the SIMD: W x 48 x iters slots
+    const double cyc_slot = base_ms > 0 ? 16.0 * ms / base_ms : 0.0;   // cycles per slot of the SIMD (all W waves' slots in turn)
+    printf("%-36s W=%d: %7.3f ms/launch  %6.2f cycles per slot of the SIMD", what, W, ms, cyc_slot);
+    if (NS > 0) printf("  = %5.2f per scalar instruction of the SIMD, %5.2f of the CU", cyc_slot / NS, cyc_slot / NS / 4.0);
+    printf("\n");
+    fflush(stdout);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipFree(d);
+    (void)hipFree(st);
+    return ms;
+}
+
+template <int W>
+void sweep_scalar() {
+    printf("---- scalar ALU, %d wave(s) per SIMD, one workgroup per CU (the MFMA-only line calibrates: 16 cycles per slot)\n", W);
+    const double base = run_scalar<W, 0, 0, true>("MFMA only", 0.0);
+    run_scalar<W, 0, 0, true>("MFMA only (calibrated)", base);
+    run_scalar<W, 8, 0, false>("[8 SALU] alone", base);
+    run_scalar<W, 4, 0, false>("[4 SALU] alone", base);
+    run_scalar<W, 0, 4, false>("[4 VALU] alone", base);
+    run_scalar<W, 4, 4, false>("[4 VALU, 4 SALU]", base);
+    run_scalar<W, 8, 4, false>("[4 VALU, 8 SALU]", base);
+    run_scalar<W, 10, 4, false>("[4 VALU, 10 SALU] (an empty ticket's mix)", base);
+    run_scalar<W, 4, 0, true>("[1 MFMA, 4 SALU]", base);
+    run_scalar<W, 8, 0, true>("[1 MFMA, 8 SALU]", base);
+    run_scalar<W, 4, 4, true>("[1 MFMA, 4 VALU, 4 SALU]", base);
+    run_scalar<W, 8, 4, true>("[1 MFMA, 4 VALU, 8 SALU]", base);
+}
+
 static double g_base[4];   // ms per trip of the MFMA-only stream, by W
 
 template <int W, int NV, int MODE, bool kMfma = true>
@@ -256,6 +364,12 @@ int main(int argc, char** argv) {
         sweep_lds<1>();
         sweep_lds<2>();
         sweep_lds<3>();
+        return 0;
+    }
+    if (argc > 1 && argv[1][0] == 's') {
+        sweep_scalar<1>();
+        sweep_scalar<2>();
+        sweep_scalar<3>();
         return 0;
     }
     sweep<1>();

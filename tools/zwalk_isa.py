@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Instruction classes per basic block of one z-walk instantiation (cross-compiled ISA; no GPU):
-   python3 tools/zwalk_isa.py [mangled-name substring, default the head-only <float,1,2,12> kernel] [--dump LABEL]"""
+   python3 tools/zwalk_isa.py [mangled-name substring, default the head-only <float,1,2,12> kernel] [--dump LABEL]
+   python3 tools/zwalk_isa.py --path LABEL,LABEL,...    the classes summed over the named blocks: one path through the ticket
+                                                        loop, e.g. an all-empty ticket (the labels are read off the listing)"""
 import re, subprocess, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 want = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else "i8z_kernelIfLi1ELi2ELi12ELb0E"
 dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
+path = sys.argv[sys.argv.index("--path") + 1].split(",") if "--path" in sys.argv else None
 out = os.path.join(ROOT, "build", "asm", "conv_i8s.s")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 if "--no-build" not in sys.argv:
@@ -39,6 +42,15 @@ for l in body:
 blocks.append((cur, cnt))
 if dump:
     print("\n".join(text.get(dump, ["(no such block)"])))
+elif path:
+    by = dict(blocks)
+    tot = {}
+    for b in path:
+        if b not in by: sys.exit("no such block: " + b)
+        for k, v in by[b].items():
+            if k == "br": tot["branches"] = tot.get("branches", 0) + len(v)
+            else: tot[k] = tot.get(k, 0) + v
+    print(len(path), "blocks:", " ".join(f"{k}={v}" for k, v in sorted(tot.items())), " (SALU includes the branches)")
 else:
     tot = {}
     for b, c in blocks:
