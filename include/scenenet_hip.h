@@ -518,6 +518,26 @@ size_t sn_conv_corr_ws_bytes(int x_dtype, int B, int Z, int X, int Y, int kz, in
 int sn_conv_corr_ws(const void* x, int x_dtype, const void* gout, const void* out, int g_dtype, int B, int Z, int X,
                     int Y, int kz, int kx, int ky, void* ws, size_t ws_bytes, float* C, sn_stream_t stream);
 
+/* What sn_conv_corr_ws would launch for these arguments under the options in force now ("corr_dense",
+ * "corr_sparse_tile_bytes"), given a workspace of sn_conv_corr_ws_bytes(...) and pointers aligned the way a fresh
+ * allocation is: host arithmetic only, from the planners the launches themselves call; no launch, no device.
+ * plan8 (8 x int32, host memory):
+ *   [0] kernel: 0 the thread-per-tap kernel, 1 the fp32-MFMA GEMM form (K4), 2 the gather over the set voxels (K4s)
+ *   [1] input rows per job (the thread-per-tap kernel: x extent of its tile, 8)
+ *   [2] row tiles per plane
+ *   [3] jobs (the thread-per-tap kernel: tiles)
+ *   [4] workgroups launched (persistent for K4 / K4s: job, job + [4], ... run on one workgroup; each writes one partial row)
+ *   [5] the kz instantiation of the kernel: 9 (kz <= 9) or 16; 0 for the thread-per-tap kernel
+ *   [6] dynamic LDS bytes per workgroup
+ *   [7] flags: bit 0 Y admits the four-element staging loads (K4: Y % 4 == 0; K4s: also the delta tile within 4096
+ *       elements), bit 1 the list kernel's 8-byte loads (K4s: Y % 8 == 0), bit 2 K4 runs every K step of a non-empty row
+ *       (more than 32 steps: Y > 128), bit 3 the gather has more than one group of threads (kx ky <= 256)
+ * Returns SN_OK, SN_ERR_INVALID_ARG (null plan8, an extent <= 0, unknown x_dtype / g_dtype) or SN_ERR_UNSUPPORTED where
+ * sn_conv_corr_ws returns it (bf16 gradients with a kernel extent > 16, a kernel too large for the thread-per-tap tile).
+ * No reference counterpart (autograd has no plan to ask about): what lets tests/test_gpu_corr_plans.py name the fork each
+ * of its shapes is there for. */
+int sn_conv_corr_plan(int x_dtype, int g_dtype, int B, int Z, int X, int Y, int kz, int kx, int ky, int32_t* plan8);
+
 /* Generator Jacobians: dparams [G, SN_NPARAM] f32 = d<dW, bank(params)>/dparams for dW [G,kz,kx,ky] f32
  * (apex has no gradient: it is truncated to an index, arrow.py:235, and non-trainable, arrow.py:134). */
 int sn_geneo_bank_bwd(const float* params, const int32_t* kinds, int G, int kz, int kx, int ky,

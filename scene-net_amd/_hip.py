@@ -76,6 +76,7 @@ SYMBOLS = {
     "sn_conv_corr_blocks": (c_int, [_I, _I, _I, _I]),
     "sn_conv_corr_ws_bytes": (ctypes.c_size_t, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "sn_conv_corr_ws": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P]),
+    "sn_conv_corr_plan": (c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sn_geneo_bank_lambdas": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "sn_geneo_bank_bwd": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "sn_geneo_backward": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
@@ -985,6 +986,43 @@ def conv_corr(x: torch.Tensor, gout: torch.Tensor, out: Optional[torch.Tensor], 
                                 _DT[gout.dtype], B, Z, X, Y, kz, kx, ky, _ptr(ws), nbytes, _ptr(C), _stream())
     _check(rc, "sn_conv_corr_ws")
     return C
+
+
+class CorrPlan(NamedTuple):
+    """sn_conv_corr_plan's eight words (include/scenenet_hip.h)."""
+    kernel: str          # "taps" (thread per tap) | "gemm" (K4) | "gather" (K4s)
+    rows: int            # input rows per job
+    row_tiles: int       # row tiles per plane
+    jobs: int
+    workgroups: int
+    kzmax: int           # 9 | 16 (0: thread per tap)
+    lds_bytes: int
+    vec: bool            # Y admits the four-element staging loads
+    list_vec: bool       # the list kernel's 8-byte loads
+    every_step: bool     # K4 runs every K step of a non-empty row
+    multi_group: bool    # the gather has more than one group
+
+
+CORR_PLAN_KERNELS = ("taps", "gemm", "gather")
+
+
+def conv_corr_plan(x, kernel_size: Sequence[int], g_dtype: torch.dtype = torch.float32) -> CorrPlan:
+    """What conv_corr(x, gout, out, kernel_size) would launch under the options in force (sn_conv_corr_plan: host only, no
+    launch, no device needed).  x: a [B,1,Z,X,Y] tensor on any device, or (dtype, shape); g_dtype: float32 | bfloat16."""
+    dtype, shape = (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else (x[0], tuple(x[1]))
+    if len(shape) != 5 or shape[1] != 1:
+        raise HipLibraryError(f"x must be [B,1,Z,X,Y] (got {shape})")
+    if dtype not in _DT or dtype == torch.bfloat16:
+        raise HipLibraryError(f"x dtype {dtype} unsupported (f32, f64, u8, bool)")
+    if g_dtype not in (torch.float32, torch.bfloat16):
+        raise HipLibraryError(f"g_dtype must be float32 or bfloat16 (got {g_dtype})")
+    B, _, Z, X, Y = (int(v) for v in shape)
+    kz, kx, ky = (int(k) for k in kernel_size)
+    p = (ctypes.c_int32 * 8)()
+    _check(load().sn_conv_corr_plan(_DT[dtype], _DT[g_dtype], B, Z, X, Y, kz, kx, ky, ctypes.cast(p, c_void_p)),
+           "sn_conv_corr_plan")
+    return CorrPlan(CORR_PLAN_KERNELS[p[0]], int(p[1]), int(p[2]), int(p[3]), int(p[4]), int(p[5]), int(p[6]),
+                    bool(p[7] & 1), bool(p[7] & 2), bool(p[7] & 4), bool(p[7] & 8))
 
 
 @_on_tensor_device

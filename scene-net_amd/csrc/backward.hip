@@ -18,6 +18,7 @@ int corr_sparse_launch(const void* x, const void* gout, const void* out, int g_d
                        int kx, int ky, void* ws, float* C, hipStream_t s);
 int corr_mfma_launch(const void* x, int x_dtype, const void* gout, const void* out, int g_dtype, int B, int Z, int X,
                      int Y, int kz, int kx, int ky, float* partial_ws, float* C, hipStream_t s);
+int corr_plan_words(int kernel, int B, int Z, int X, int Y, int kz, int kx, int ky, int32_t* plan8);
 }  // namespace sn
 
 namespace {
@@ -271,6 +272,31 @@ __global__ __launch_bounds__(256) void geneo_bank_bwd_kernel(const float* __rest
     }
 }
 
+// The thread-per-tap kernel's launch: tiles per axis, workgroups (= partial rows) and dynamic LDS.  sn_conv_corr_t and
+// the plan query (sn_conv_corr_plan) both call this.
+struct TapPlan {
+    int nzt, nxt, nyt, nblk;
+    size_t lds;
+};
+TapPlan tap_plan(int B, int Z, int X, int Y, int kz, int kx, int ky) {
+    TapPlan t;
+    t.nzt = (Z + TZ - 1) / TZ; t.nxt = (X + TX - 1) / TX; t.nyt = (Y + TY - 1) / TY;
+    t.lds = ((size_t)(TZ + kz - 1) * (TX + kx - 1) * (TY + ky - 1) + (size_t)TZ * TX * TY) * sizeof(float);
+    t.nblk = B * t.nzt * t.nxt * t.nyt;
+    return t;
+}
+
+// Which kernel sn_conv_corr_t runs: 1 the matrix-core kernel (corr.hip) for every kernel extent <= 16 it has a plan for,
+// 0 the thread-per-tap kernel for the rest, or the error it returns (`who` names the entry point in the message).
+int corr_t_route(const char* who, int g_dtype, int B, int Z, int X, int Y, int kz, int kx, int ky) {
+    if (sn::corr_mfma_supported(kz, kx, ky) && sn::corr_mfma_rows(B, Z, X, Y, kz, kx, ky) > 0) return 1;
+    if (g_dtype != SN_F32)
+        return sn::fail(SN_ERR_UNSUPPORTED, "%s: bf16 gradients need a kernel extent <= 16 per axis", who);
+    if (tap_plan(B, Z, X, Y, kz, kx, ky).lds > 150 * 1024)
+        return sn::fail(SN_ERR_UNSUPPORTED, "%s: kernel %dx%dx%d too large", who, kz, kx, ky);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int sn_conv_corr_t(const void* x, int x_dtype, const void* gout_v, const void* out_v, int g_dtype, int B,
@@ -281,18 +307,16 @@ extern "C" int sn_conv_corr_t(const void* x, int x_dtype, const void* gout_v, co
         return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_corr: non-positive extent");
     if (g_dtype != SN_F32 && g_dtype != SN_BF16)
         return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_corr_t: g_dtype %d (SN_F32 | SN_BF16)", g_dtype);
-    // matrix-core kernel (corr.hip) for every kernel extent <= 16; the thread-per-tap kernel below serves the rest
-    if (sn::corr_mfma_supported(kz, kx, ky) && sn::corr_mfma_rows(B, Z, X, Y, kz, kx, ky) > 0)
+    const int route = corr_t_route("sn_conv_corr_t", g_dtype, B, Z, X, Y, kz, kx, ky);
+    if (route < 0) return route;
+    if (route == 1)
         return sn::corr_mfma_launch(x, x_dtype, gout_v, out_v, g_dtype, B, Z, X, Y, kz, kx, ky, partial_ws, C,
                                     sn::as_stream(stream));
-    if (g_dtype != SN_F32)
-        return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_corr_t: bf16 gradients need a kernel extent <= 16 per axis");
     const float* gout = (const float*)gout_v;
     const float* out = (const float*)out_v;
-    const int nzt = (Z + TZ - 1) / TZ, nxt = (X + TX - 1) / TX, nyt = (Y + TY - 1) / TY;
-    const size_t lds = ((size_t)(TZ + kz - 1) * (TX + kx - 1) * (TY + ky - 1) + (size_t)TZ * TX * TY) * sizeof(float);
-    if (lds > 150 * 1024) return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_corr: kernel %dx%dx%d too large", kz, kx, ky);
-    const int nblk = B * nzt * nxt * nyt, ntaps = kz * kx * ky;
+    const TapPlan tp = tap_plan(B, Z, X, Y, kz, kx, ky);
+    const int nzt = tp.nzt, nxt = tp.nxt, nyt = tp.nyt, nblk = tp.nblk, ntaps = kz * kx * ky;
+    const size_t lds = tp.lds;
     hipStream_t s = sn::as_stream(stream);
 #define SN_CORR(XT)                                                                                               \
     do {                                                                                                          \
@@ -344,6 +368,33 @@ extern "C" int sn_conv_corr_ws(const void* x, int x_dtype, const void* gout, con
     if (sparse && ws_bytes >= sparse)
         return sn::corr_sparse_launch(x, gout, out, g_dtype, B, Z, X, Y, kz, kx, ky, ws, C, sn::as_stream(stream));
     return sn_conv_corr_t(x, x_dtype, gout, out, g_dtype, B, Z, X, Y, kz, kx, ky, (float*)ws, C, stream);
+}
+
+extern "C" int sn_conv_corr_plan(int x_dtype, int g_dtype, int B, int Z, int X, int Y, int kz, int kx, int ky,
+                                 int32_t* plan8) {
+    if (!plan8) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_corr_plan: null plan8");
+    if (B <= 0 || Z <= 0 || X <= 0 || Y <= 0 || kz <= 0 || kx <= 0 || ky <= 0)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_corr_plan: non-positive extent");
+    if (g_dtype != SN_F32 && g_dtype != SN_BF16)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_corr_plan: g_dtype %d (SN_F32 | SN_BF16)", g_dtype);
+    if (x_dtype != SN_F32 && x_dtype != SN_F64 && x_dtype != SN_U8 && x_dtype != SN_OCC8)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_corr_plan: x_dtype %d", x_dtype);
+    // the order of sn_conv_corr_ws with a workspace of sn_conv_corr_ws_bytes: the gather where it has a plan ...
+    if (sn::corr_sparse_ws_bytes(x_dtype, B, Z, X, Y, kz, kx, ky) &&
+        sn::corr_plan_words(2, B, Z, X, Y, kz, kx, ky, plan8))
+        return SN_OK;
+    // ... else sn_conv_corr_t's two kernels
+    const int route = corr_t_route("sn_conv_corr_plan", g_dtype, B, Z, X, Y, kz, kx, ky);
+    if (route < 0) return route;
+    if (route == 1) {
+        if (!sn::corr_plan_words(1, B, Z, X, Y, kz, kx, ky, plan8))
+            return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_corr_plan: shape outside the MFMA correlation kernel");
+        return SN_OK;
+    }
+    const TapPlan tp = tap_plan(B, Z, X, Y, kz, kx, ky);
+    const int32_t w[8] = {0, TX, tp.nxt, tp.nblk, tp.nblk, 0, (int32_t)tp.lds, 0};
+    for (int i = 0; i < 8; ++i) plan8[i] = w[i];
+    return SN_OK;
 }
 
 extern "C" int sn_conv_corr_blocks(int B, int Z, int X, int Y) {

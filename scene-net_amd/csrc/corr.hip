@@ -28,6 +28,7 @@ int corr_mfma_launch(const void* x, int x_dtype, const void* gout, const void* o
 size_t corr_sparse_ws_bytes(int x_dtype, int B, int Z, int X, int Y, int kz, int kx, int ky);
 int corr_sparse_launch(const void* x, const void* gout, const void* out, int g_dtype, int B, int Z, int X, int Y, int kz,
                        int kx, int ky, void* ws, float* C, hipStream_t s);
+int corr_plan_words(int kernel, int B, int Z, int X, int Y, int kz, int kx, int ky, int32_t* plan8);
 }  // namespace sn
 
 namespace {
@@ -43,7 +44,7 @@ struct CorrShape {
     int YK;               // K extent: Y rounded up to 32 (zero filled)
     int DR, DS;           // delta tile: rows, row stride (floats)
     int XS;               // input tile row stride (floats)
-    int vec;              // Y % 4 == 0 and 16-byte (byte input: 4-byte) aligned pointers: 4-element loads
+    int vec;              // Y % 4 == 0 (plan) and 16-byte (byte input: 4-byte) aligned pointers (launch): 4-element loads
 };
 
 template <typename T>
@@ -295,6 +296,7 @@ bool plan(int B, int Z, int X, int Y, int kz, int kx, int ky, CorrShape* s, size
     s->B = B; s->Z = Z; s->X = X; s->Y = Y; s->kz = kz; s->kx = kx; s->ky = ky;
     s->pz = (kz - 1) / 2; s->px = (kx - 1) / 2; s->py = (ky - 1) / 2;
     s->YK = (Y + 31) / 32 * 32;
+    s->vec = (Y % 4 == 0);
     s->DS = s->YK + 4;
     s->XS = s->YK + 16;
     const size_t budget = 150 * 1024;
@@ -358,6 +360,16 @@ struct SparseShape {
     int dbg;           // wrong-result timing switch (SN_CONV_DEBUG builds only: SN_K4S_SKIP): 1 no job does anything, 2 no gather
 };
 
+// delta = gout d relu(tanh(s))/ds from the forward output o, for both staging forms of the gather: the square is rounded
+// before the subtraction.  (Left to itself hipcc packed the four-element form's squares into v_pk_mul_f32 + v_sub_f32 and
+// contracted the element form's into one v_fma_f32, so a pointer that broke the four-element loads changed the last bit
+// of a delta; this is the four-element form's arithmetic -- the training shapes' -- for both.)
+__device__ __forceinline__ float gather_delta(float g, float o) {
+    float oo = o * o;
+    asm volatile("" : "+v"(oo));
+    return (o > 0.f) ? g * (1.f - oo) : 0.f;
+}
+
 // list index of (b, z', tile xt); the gather reads the lists of z' = z + dz - pz
 __device__ __forceinline__ int list_index(const SparseShape& s, int b, int z, int xt) { return (b * s.Z + z) * s.nxt + xt; }
 
@@ -420,7 +432,9 @@ __global__ __launch_bounds__(kSpListThreads) void corr_lists_kernel(const uint8_
         }
     }
     // padding: the last quad of every group's walk is complete; its entries read the zero tail of the tile
-    if (tid < 4 * s.groups) list[total + tid] = (uint16_t)((s.DR * s.P + (s.kx - 1) * s.P + (s.ky - 1)) * 4);
+    // (a quad is up to 4 x 512 entries -- kx ky = 1 -- and the workgroup has 256 threads: a loop, not one entry per thread)
+    for (int i = tid; i < 4 * s.groups; i += kSpListThreads)
+        list[total + i] = (uint16_t)((s.DR * s.P + (s.kx - 1) * s.P + (s.ky - 1)) * 4);
     // what the gather needs to know: the list's length in ROUNDS (quads per group) -- no division on its side
     if (tid == 0) counts[li] = (total + 4 * s.groups - 1) / (4 * s.groups);
 }
@@ -559,7 +573,7 @@ __global__ __launch_bounds__(kSpThreads, 6) void corr_gather_kernel(const DT* __
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             float d = g[4 * u + k];
-                            if (out) d = (o[4 * u + k] > 0.f) ? d * (1.f - o[4 * u + k] * o[4 * u + k]) : 0.f;
+                            if (out) d = gather_delta(d, o[4 * u + k]);
                             dst[k] = outside ? 0.f : d;
                         }
                     }
@@ -571,7 +585,7 @@ __global__ __launch_bounds__(kSpThreads, 6) void corr_gather_kernel(const DT* __
                     if (e < nel) {
                         const int rr = (int)__umulhi((unsigned)e, s.y_magic), y = e - rr * s.Y;
                         float d = g[u];
-                        if (out) d = (o[u] > 0.f) ? d * (1.f - o[u] * o[u]) : 0.f;
+                        if (out) d = gather_delta(d, o[u]);
                         if ((unsigned)(cur.e_lo + e) >= e_hi) d = 0.f;   // a row outside the grid
                         dl[rr * s.P + (s.ky - 1 - s.py) + y] = d;
                     }
@@ -698,6 +712,9 @@ bool plan_sparse(int B, int Z, int X, int Y, int kz, int kx, int ky, int tile_by
     s->TXR = txr;
     s->nxt = (X + txr - 1) / txr;
     s->DR = txr + kx - 1;
+    s->vec = (Y % 8 == 0);
+    // quads of the delta tile: 2 x 4 x 512 elements at most, whole rows of a multiple of four
+    s->vec4 = (Y % 4 == 0) && (s->DR * Y <= 8 * kSpThreads);
     int P = Y + ky - 1;
     while (P % 64 != ky % 64) ++P;
     s->P = P;
@@ -747,6 +764,27 @@ int sn::corr_mfma_rows(int B, int Z, int X, int Y, int kz, int kx, int ky) {
     return plan(B, Z, X, Y, kz, kx, ky, &s, &lds, &grid) ? grid : 0;
 }
 
+// sn_conv_corr_plan's view of the two kernels of this file (kernel 1: K4, 2: K4s under the tile-bytes option in force):
+// 1 = plan8 filled from the planner the launch calls, 0 = that planner refuses the shape.  Host arithmetic only.
+int sn::corr_plan_words(int kernel, int B, int Z, int X, int Y, int kz, int kx, int ky, int32_t* plan8) {
+    if (kernel == 1) {
+        CorrShape s;
+        size_t lds;
+        int grid;
+        if (!plan(B, Z, X, Y, kz, kx, ky, &s, &lds, &grid)) return 0;
+        const int32_t w[8] = {1, s.TXR, s.nxt, s.njobs, grid, kz <= 9 ? 9 : 16, (int32_t)lds,
+                              (s.vec ? 1 : 0) | ((s.YK >> 2) > 32 ? 4 : 0)};
+        for (int i = 0; i < 8; ++i) plan8[i] = w[i];
+        return 1;
+    }
+    SparsePlan p;
+    if (!plan_sparse(B, Z, X, Y, kz, kx, ky, sn::option(sn::kOptCorrSparseTileBytes), &p)) return 0;
+    const int32_t w[8] = {2, p.s.TXR, p.s.nxt, p.s.njobs, p.grid, kz <= 9 ? 9 : 16, (int32_t)p.lds_bytes,
+                          (p.s.vec4 ? 1 : 0) | (p.s.vec ? 2 : 0) | (p.s.groups > 1 ? 8 : 0)};
+    for (int i = 0; i < 8; ++i) plan8[i] = w[i];
+    return 1;
+}
+
 size_t sn::corr_sparse_ws_bytes(int x_dtype, int B, int Z, int X, int Y, int kz, int kx, int ky) {
     if (x_dtype != SN_OCC8 || sn::option(sn::kOptCorrDense)) return 0;
     SparsePlan p;
@@ -759,10 +797,10 @@ int sn::corr_sparse_launch(const void* x, const void* gout, const void* out, int
     if (!plan_sparse(B, Z, X, Y, kz, kx, ky, sn::option(sn::kOptCorrSparseTileBytes), &p))
         return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_corr_ws: shape outside the sparse correlation kernels");
     SparseShape& s = p.s;
-    s.vec = (Y % 8 == 0) && ((uintptr_t)x % 8 == 0);
-    {   // quads of the delta tile: 2 x 4 x 512 elements at most, whole rows of a multiple of four, aligned pointers
+    s.vec = s.vec && ((uintptr_t)x % 8 == 0);
+    {   // the vector forms the plan admits also need aligned pointers
         const size_t ga = g_dtype == SN_BF16 ? 8 : 16;
-        s.vec4 = (Y % 4 == 0) && (s.DR * Y <= 8 * kSpThreads) && ((uintptr_t)gout % ga == 0) && (!out || (uintptr_t)out % ga == 0);
+        s.vec4 = s.vec4 && ((uintptr_t)gout % ga == 0) && (!out || (uintptr_t)out % ga == 0);
     }
     s.dbg = sn::debug_env_int("SN_K4S_SKIP");
     float* partial = reinterpret_cast<float*>(ws);
@@ -802,8 +840,7 @@ int sn::corr_mfma_launch(const void* x, int x_dtype, const void* gout, const voi
         return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_corr: shape outside the MFMA correlation kernel");
     const size_t xa = (x_dtype == SN_U8 || x_dtype == SN_OCC8) ? 4 : 16;
     const size_t ga = g_dtype == SN_BF16 ? 8 : 16;
-    s.vec = (Y % 4 == 0) && ((uintptr_t)x % xa == 0) && ((uintptr_t)gout % ga == 0) &&
-            (!out || (uintptr_t)out % ga == 0);
+    s.vec = s.vec && ((uintptr_t)x % xa == 0) && ((uintptr_t)gout % ga == 0) && (!out || (uintptr_t)out % ga == 0);
 #define SN_CORR_LAUNCH(XT, KZMAX)                                                                                 \
     do {                                                                                                          \
         if (g_dtype == SN_BF16) {                                                                                 \

@@ -23,7 +23,8 @@ def _declared_symbols():
 def test_header_symbols_are_bound_and_exported():
     declared = _declared_symbols()
     assert {"sn_geneo_bank", "sn_conv_bank", "sn_voxel_bbox", "sn_voxel_desc", "sn_voxel_scatter",
-            "sn_voxel_finalize", "sn_voxel_occupancy", "sn_voxel_prepare", "sn_last_error", "sn_version"} <= declared
+            "sn_voxel_finalize", "sn_voxel_occupancy", "sn_voxel_prepare", "sn_last_error", "sn_version",
+            "sn_conv_corr_plan"} <= declared
     assert declared == set(_hip.SYMBOLS), "ctypes table and header disagree"
     lib = ctypes.CDLL(_hip.LIB_PATH)
     for name in declared:
@@ -59,6 +60,13 @@ def test_argument_checks_need_no_gpu():
                                   None) == -1  # f64 output not offered
     assert lib.sn_voxel_prepare(p, p, 1, 64, 64, 0, 1, p, None, p, None) == -1
     assert lib.sn_voxel_finalize(p, None, 1, 4, 4, 4, p, None, p, None, None, None) == -1  # gt w/o towers
+    # the correlation's plan query: host arithmetic, refused like the launch it describes
+    assert lib.sn_conv_corr_plan(3, 0, 1, 8, 8, 16, 3, 3, 3, None) == -1
+    assert b"null" in lib.sn_last_error()
+    assert lib.sn_conv_corr_plan(3, 0, 1, 8, 0, 16, 3, 3, 3, p) == -1
+    assert lib.sn_conv_corr_plan(0, 4, 1, 8, 8, 16, 3, 3, 17, p) == -2   # bf16 gradients, ky > 16
+    assert b"bf16" in lib.sn_last_error()
+    assert lib.sn_conv_corr_plan(3, 0, 1, 8, 8, 16, 3, 3, 3, p) == 0
     assert lib.sn_grid_to_points(None, 0, 4, 4, 4, None, None, p, None) == -1
     assert lib.sn_grid_to_points(p, 0, 4, 0, 4, None, None, p, None) == -1   # empty grid
     assert b"empty" in lib.sn_last_error()

@@ -324,6 +324,27 @@ def test_round3_entry_points_are_bound():
         int(lib.sn_conv_corr_ws_bytes(_hip.SN_F32, 32, 64, 64, 64, 9, 9, 9)) > 0
 
 
+def test_corr_plan_entry_point_is_bound():
+    """sn_conv_corr_plan is declared, exported and bound; conv_corr_plan returns its eight words as a named tuple, from a
+    tensor or from (dtype, shape), under the options in force"""
+    from scene_net_amd import _hip
+    lib = _hip.load()
+    assert "sn_conv_corr_plan" in _hip.SYMBOLS and hasattr(lib, "sn_conv_corr_plan")
+    assert lib.sn_version() >= 105
+    x = torch.zeros((2, 1, 8, 8, 16), dtype=torch.bool)
+    with _hip.options(corr_dense=0, corr_sparse_tile_bytes=0):
+        p = _hip.conv_corr_plan(x, (3, 3, 3))
+        assert p == _hip.conv_corr_plan((torch.bool, (2, 1, 8, 8, 16)), (3, 3, 3), torch.float32)
+        assert p._fields == ("kernel", "rows", "row_tiles", "jobs", "workgroups", "kzmax", "lds_bytes", "vec", "list_vec",
+                             "every_step", "multi_group")
+        assert (p.kernel, p.rows, p.row_tiles, p.jobs, p.workgroups, p.kzmax) == ("gather", 8, 1, 16, 16, 9)
+    with _hip.options(corr_dense=1):
+        assert _hip.conv_corr_plan(x, (3, 3, 3), torch.bfloat16).kernel == "gemm"
+    assert _hip.conv_corr_plan(x.float(), (3, 3, 17)).kernel == "taps"
+    with pytest.raises(_hip.HipLibraryError):
+        _hip.conv_corr_plan(x.float(), (3, 3, 17), torch.bfloat16)
+
+
 def test_tracked_parameters_stay_ordinary_parameters():
     """The model's parameters carry a Parameter subclass that counts `.data` accesses (scene_net._TrackedParameter: the caches
     see a write through .data).  It must change nothing a user of nn.Parameter can observe: isinstance, repr, state_dict keys
