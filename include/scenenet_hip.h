@@ -1381,6 +1381,58 @@ int sn_class_paint(const double* classes, const int64_t* offsets, int64_t total,
                    const double* table, int T, double* colors, uint16_t* rgb, double* unique, int U_max, int64_t* n_unique,
                    int64_t* short_table, sn_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * K19 -- scan merge: the predictions of K tiles put back on the whole scan they were cut from, in one pass.
+ * replaces: sn_gather_points over the cropped rows followed by crops.merge_to_scan (five torch launches, a scatter_reduce
+ *           through floating-point atomics, the crops' src column) -- the last step of "a corridor scan in, a probability
+ *           per scan point out".  (Build-defined: the reference has no whole-scan step.)
+ *
+ *   grid     [B, channels, nz, nx, ny] of `dtype` (SN_F32 | SN_F64): the tiles' predictions
+ *   desc     [B, SN_DESC_LEN(nx,ny,nz)]: the voxelisation's descriptor of every tile, n-mode or size-mode
+ *   pts      [n,3] f64: the scan;  regions [K,4] f64, kinds [K] i32 (nullable: all discs): exactly K9's
+ *   tile_of  [K] i32 (nullable): the tile of region k.  Null: tile k, and B == K is required.  A value outside 0..B-1: the
+ *            region has no tile and covers nothing (how the empty regions a batch dropped are expressed; device memory,
+ *            so no entry is refused).  Two regions may share a tile.
+ *   out      [channels, n] of `dtype`;  cover [n] i32 (nullable)
+ *
+ * Covering.  Region k COVERS point i iff (1) k has a tile, (2) the point is a member of k by K9's test taken literally --
+ * the same text with the same roundings, z takes no part, a NaN is a member of nothing, a kinds value other than
+ * SN_CROP_DISC / SN_CROP_BOX makes the region empty -- and (3) the point bins inside tile tile_of[k]'s edge table by
+ * sn_gather_points' rule: at or below the first edge of an axis (-inf included) is bin 0; above the last edge, +inf or NaN
+ * is outside; a size-mode padding cell is outside.  A member that bins outside is NOT covered by that tile: it does not
+ * contribute `fill` (sn_gather_points + merge_to_scan let it compete with the value `fill`).
+ * cover[i] is the number of covering regions; a point with none gets `fill` in every channel.
+ *   SN_MERGE_MAX       per channel the largest covering value; NaN if any covering value is NaN (what
+ *                      scatter_reduce(amax) gives: a kernel that reports through NaN outputs must surface).
+ *   SN_MERGE_MEAN      the covering values widened to fp64 and added in ascending region index, the sum divided by the count
+ *                      with one rounding, the quotient rounded to `dtype`.
+ *   SN_MERGE_INTERIOR  every channel from the covering region with the largest DEPTH: the first covering region (ascending
+ *                      index) is held, a later one replaces it iff its depth > the held depth, so ties go to the lowest
+ *                      index (and a NaN depth neither replaces nor is replaced).  Depth is fp64, every operation rounded
+ *                      once, never contracted:
+ *                        box (xmin, ymin, xmax, ymax):  min(min(x - xmin, xmax - x), min(y - ymin, ymax - y)), min(a, b) =
+ *                                                       a < b ? a : b
+ *                        disc (cx, cy, r):              sqrt(R2) - sqrt(s), R2 = fl(r*r), s = fl(fl(dx*dx) + fl(dy*dy)) -- the
+ *                                                       very two numbers the membership test compares; both roots correctly
+ *                                                       rounded
+ *                      Depth follows the REGION's geometry, not the grid's: the grid is built from the members' bounding
+ *                      cube, which may end short of the region's rim.
+ * One launch; no workspace, no atomics, no memset, no allocation, no synchronisation: capturable, and one thread owns one
+ * scan point, so no result depends on scheduling.  regions, kinds, tile_of and desc are device memory: a replay follows
+ * their current contents.
+ * SN_ERR_INVALID_ARG (before the launch): a null grid / desc / pts / regions / out; n, K, B, channels or an extent <= 0;
+ * rule outside 0..2; dtype not F32 / F64; tile_of null with B != K; pts / regions / desc not 8-byte, kinds / tile_of /
+ * cover not 4-byte, grid / out not element aligned.  SN_ERR_UNSUPPORTED: n > 2^36, K > 65536, channels > 65535, an edge
+ * table above 64 KiB (sn_gather_points' bound).
+ * ------------------------------------------------------------------------- */
+#define SN_MERGE_MAX      0
+#define SN_MERGE_MEAN     1
+#define SN_MERGE_INTERIOR 2
+int sn_scan_merge(const void* grid, int dtype, int channels, int B, int nx, int ny, int nz, const double* desc,
+                  const double* pts, int64_t n, const double* regions, const int32_t* kinds,
+                  const int32_t* tile_of, int K, int rule, double fill, void* out, int32_t* cover,
+                  sn_stream_t stream);
+
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ from .tower_score import (TowerCentroids, TowerDetectionMetrics, TowerMatches, c
                           tower_centroids, tower_detection_values)
 from .crops import (ScanCrops, crop_at_locations, crop_regions, crop_tower_radius, crop_tower_samples, crop_two_towers,
                     lattice_regions, merge_to_scan)
+from .scan_merge import ScanSegmentation, classify_las, scan_predictions, segment_scan
 from .clusters import PointClusters, cluster_points, crop_two_towers_samples, extract_towers, select_object
 from .census import (RegionCensus, accept_kinds, crop_accepted, crop_ground_samples, crop_pole_slabs, pole_radius_samples,
                      region_census, scan_has_class, slab_regions, watch_equal, watch_trunc)
@@ -45,7 +46,7 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "PointBatch", "VoxelGrids", "ScenePipeline", "CapturedPipeline", "CapturedTrainingStep", "allreduce_flat_grads", "shard_range", "TS40KTiles", "batch_to_device", "pack_csr",
            "point_predictions", "split_tile", "TileStream", "TileRing", "scan_tiles", "BinarySegmentationMetrics", "BinarySegmentationCurve", "init_metrics", "TowerProposals", "tower_proposals", "filter_towers", "aggregate_centroids", "TowerCentroids", "TowerMatches", "TowerDetectionMetrics",
            "tower_centroids", "get_tower_proposals", "compute_euc_dists", "tower_detection_values", "ScanCrops", "crop_regions", "crop_at_locations",
-           "crop_tower_radius", "crop_two_towers", "crop_tower_samples", "lattice_regions", "merge_to_scan", "PointClusters", "cluster_points", "select_object", "extract_towers",
+           "crop_tower_radius", "crop_two_towers", "crop_tower_samples", "lattice_regions", "merge_to_scan", "ScanSegmentation", "scan_predictions", "segment_scan", "classify_las", "PointClusters", "cluster_points", "select_object", "extract_towers",
            "crop_two_towers_samples", "RegionCensus", "region_census", "watch_equal", "watch_trunc", "accept_kinds", "crop_accepted",
            "slab_regions", "crop_ground_samples", "crop_pole_slabs", "pole_radius_samples", "scan_has_class", "LasHeader", "LasReader", "LasScan",
            "read_las_header", "read_las", "las_to_numpy", "build_data_samples", "plan_chunks", "split_slices", "LasWriter", "LasWritten",

@@ -147,6 +147,8 @@ SYMBOLS = {
     "sn_voxel_classes": (c_int, [_P, _P, _P, ctypes.c_int64, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sn_class_census": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _P]),
     "sn_class_paint": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "sn_scan_merge": (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_int64, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P,
+                              _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -165,6 +167,7 @@ SN_KITTI_MAX_LUT, SN_KITTI_MAX_HIST = 65536, 1024
 SN_CLOUD_DENSITY, SN_CLOUD_RANGES, SN_CLOUD_MAX_R = 0, 1, 32
 SN_THIN_GROUP_NONE, SN_THIN_GROUP_Z, SN_THIN_GROUP_VOXEL = 0, 1, 2
 SN_CLASS_WORDS, SN_VOXEL_CLASSES_NO_SKIP = 2048, 1
+SN_MERGE_MAX, SN_MERGE_MEAN, SN_MERGE_INTERIOR = 0, 1, 2
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -2002,3 +2005,32 @@ def class_paint(classes: torch.Tensor, offsets: torch.Tensor, present: torch.Ten
                                _ptr(unique, torch.float64, "unique"), U_max, _ptr(n_unique, torch.int64, "n_unique"),
                                _ptr(short_table, torch.int64, "short_table"), _stream())
     _check(rc, "sn_class_paint")
+
+
+# --------------------------------------------------------------------------- #
+@_on_tensor_device
+def scan_merge(grid: torch.Tensor, desc: torch.Tensor, pts: torch.Tensor, regions: torch.Tensor,
+               kinds: Optional[torch.Tensor], tile_of: Optional[torch.Tensor], rule: int, fill: float, out: torch.Tensor,
+               cover: Optional[torch.Tensor]) -> None:
+    """sn_scan_merge: grid [B,C,nz,nx,ny] (f32|f64), desc [B, desc_len], pts [n,3] f64, regions [K,4] f64, kinds [K] i32 |
+    None, tile_of [K] i32 | None (then B == K) -> out [C, n] of the grid's dtype and cover [n] i32 | None, caller-owned.
+    One launch, no allocation, no synchronisation."""
+    if grid.dim() != 5 or grid.dtype not in (torch.float32, torch.float64):
+        raise HipLibraryError("grid must be [B,C,nz,nx,ny] float32/float64")
+    B, C, nz, nx, ny = grid.shape
+    n, K = _crop_head(pts, regions, kinds)
+    # host-side shape checks, no synchronisation: the kernel reads desc[b * desc_len + ..] and tile_of[0..K) unchecked
+    if tuple(desc.shape) != (B, desc_len(nx, ny, nz)):
+        raise HipLibraryError(f"desc must be [B, desc_len(nx, ny, nz)] = [{B}, {desc_len(nx, ny, nz)}] "
+                              f"(got {tuple(desc.shape)})")
+    if tile_of is not None and tile_of.numel() != K:
+        raise HipLibraryError("tile_of must hold one entry per region")
+    if out.dtype != grid.dtype or out.numel() < C * n:
+        raise HipLibraryError("out must hold channels * n values of the grid's dtype")
+    if cover is not None and cover.numel() < n:
+        raise HipLibraryError("cover must hold n entries")
+    rc = load().sn_scan_merge(_ptr(grid, None, "grid"), _DT[grid.dtype], C, B, nx, ny, nz, _ptr(desc, torch.float64, "desc"),
+                              _ptr(pts, torch.float64, "pts"), n, _ptr(regions, torch.float64, "regions"),
+                              _ptr(kinds, torch.int32, "kinds"), _ptr(tile_of, torch.int32, "tile_of"), K, int(rule),
+                              float(fill), _ptr(out, None, "out"), _ptr(cover, torch.int32, "cover"), _stream())
+    _check(rc, "sn_scan_merge")
