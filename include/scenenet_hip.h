@@ -627,6 +627,52 @@ int sn_criterion_backward(const void* pred, int pred_dtype, const void* gt, int 
                           const float* ranges, int H, const double* coef, const void* upstream, int up_dtype,
                           void* grad_pred, const float* pen_grad, int N, float* pen_out, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * K20  weighted pinball loss of the quantile ensemble (csrc/quantile.hip)
+ * replaces: QuantileLoss.quantile_loss + forward (core/criterions/quant_loss.py:74-102) over
+ *           WeightedMSE.get_weight_target (core/criterions/w_mse.py:114-145), which QuantileGENEOLoss.forward
+ *           (quant_loss.py:118-142) adds its penalties to.
+ *
+ * With d = gt[b,v] - pred[b,i,v] and w(gt) = bin_w at K5's bin (argmin_k |gt - ranges[k]|, first minimum, in gt's dtype;
+ * byte targets through a 256-entry table):
+ *     L = sum_{b,v} w(gt[b,v]) sum_i max(q_i d, (q_i - 1) d)  /  sum_{b,v} w(gt[b,v])
+ * -- mean(weights / mean(weights) * sum_i rho_i) over the B * n_per voxels, PER SAMPLE: the reference's
+ * `y_gt - y_pred[:, i]` broadcasts a [B,1,...] ground truth against [B,...] to [B,B,...] (every ground truth against every
+ * sample's prediction) and is this formula only at B = 1.
+ * q_i and q_i - 1 are float32 (the reference holds qs as a float32 tensor); d and rho are evaluated in the promoted type of
+ * pred and gt (fp64 when either is SN_F64, else fp32); every sum is fp64 in a fixed order (bit-reproducible).
+ * Gradient: dL/dpred[b,i,v] = up * w(gt[b,v]) / sum w * g,  g = -q_i (d > 0), 1 - q_i (d < 0), 0.5 - q_i (d == 0: torch.max
+ * hands half of the gradient to each argument at a tie), in pred's dtype.
+ * A NaN in pred or gt makes the loss NaN; the gradient at such an element is unspecified.
+ *
+ * Launch plan: forward = SN_QUANTILE_PARTS(n_per) x B workgroups (K5's: 16384 voxels per part, at most 256 parts) + one
+ * combining workgroup; backward = SN_QUANTILE_BWD_PARTS(n_per) x B workgroups (8192 voxels per part, at most 512).  A
+ * part spans ceil(n_per / parts) voxels rounded up to a multiple of 4; the 4-wide loop runs when n_per % 4 == 0, the element
+ * loop otherwise.  No atomics, no allocation; capturable.
+ * ------------------------------------------------------------------------- */
+#define SN_QUANTILE_MAX_Q 8
+#define SN_QUANTILE_PARTS(n_per) SN_LOSS_PARTS(n_per)
+#define SN_QUANTILE_BWD_PARTS(n_per) ((n_per) <= 8192 ? 1 : ((n_per) >= 8192 * 512 ? 512 : (int)(((n_per) + 8191) / 8192)))
+#define SN_QUANTILE_NSTAT(Q, H) ((Q) + (H))   /* sum_v w rho_i [Q], count of bin k [H] */
+#define SN_QUANTILE_WS_DOUBLES(B, n_per, Q, H) ((int64_t)(B) * SN_QUANTILE_PARTS(n_per) * SN_QUANTILE_NSTAT(Q, H))
+
+/* Forward.  pred [B, Q, n_per] (SN_F32 | SN_F64), gt [B, n_per] (SN_F32 | SN_F64 | SN_U8 | SN_OCC8), qs [Q] HOST floats
+ * (passed to the kernels by value), ranges / bin_w [H] f32 as in sn_loss_forward.
+ * Outputs: loss [1 + Q] f64 = {L, each quantile's share of it}; loss_f32 [1 + Q] (nullable) the same rounded once;
+ * coef [H] f64 = bin_w[k] / sum w for sn_quantile_backward; stats [B, SN_QUANTILE_NSTAT(Q, H)] f64 (per sample: the Q
+ * weighted pinball sums, then the H bin counts).  parts_ws: scratch [SN_QUANTILE_WS_DOUBLES(B, n_per, Q, H)] f64.
+ * SN_ERR_INVALID_ARG: a null pointer, B <= 0, n_per <= 0, Q outside 1..SN_QUANTILE_MAX_Q, H outside 1..SN_LOSS_MAX_BINS, an
+ * unknown dtype, a misaligned pointer (n_per % 4 == 0: 16 bytes, byte gt 4);  SN_ERR_UNSUPPORTED: SN_BF16 predictions, a q
+ * outside (0, 1), B > 65535.  All checked before any launch. */
+int sn_quantile_forward(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int B, int Q, int64_t n_per,
+                        const float* qs, const float* ranges, const float* bin_w, int H, double* parts_ws, double* stats,
+                        double* loss, float* loss_f32, double* coef, sn_stream_t stream);
+/* Backward: grad_pred [B, Q, n_per] in pred's dtype, one launch.  upstream: device scalar SN_F64 | SN_F32 (dL/dloss),
+ * NULL = 1.  Checks as sn_quantile_forward. */
+int sn_quantile_backward(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int B, int Q, int64_t n_per,
+                         const float* qs, const float* ranges, int H, const double* coef, const void* upstream,
+                         int up_dtype, void* grad_pred, sn_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------
  * K6 -- training metrics (csrc/metrics.hip)

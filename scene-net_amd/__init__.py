@@ -37,8 +37,8 @@ from .thin import (ThinnedPoints, ThinPoints, downsampling, downsampling_relativ
                    philox_uniforms, thin_points, uniform_thresholds)
 from .voxel_classes import (ClassColors, VoxelClasses, class_colors, classes_on_voxel, color_pointcloud,
                             random_class_colors, voxel_classes)
-from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss, GENEO_Loss,
-                         GENEO_Tversky_Loss, TverskyLoss, WeightedMSE)
+from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalLoss, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss,
+                         GENEO_Loss, GENEO_Tversky_Loss, IoULoss, QuantileGENEOLoss, QuantileLoss, TverskyLoss, WeightedMSE)
 
 __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cylinder_kernel", "cone_kernel",
            "neg_sphere_kernel", "GENEO_Layer", "GENEO_kernel_torch", "cylinderv2", "arrow", "negSpherev2", "Voxelization",
@@ -58,4 +58,4 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "random_class_colors",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
-           "BinaryDiceLoss_BCE"]
+           "BinaryDiceLoss_BCE", "QuantileLoss", "QuantileGENEOLoss", "FocalLoss", "IoULoss"]

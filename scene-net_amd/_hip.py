@@ -149,10 +149,13 @@ SYMBOLS = {
     "sn_class_paint": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "sn_scan_merge": (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_int64, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P,
                               _P]),
+    "sn_quantile_forward": (c_int, [_P, _I, _P, _I, _I, _I, ctypes.c_int64, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "sn_quantile_backward": (c_int, [_P, _I, _P, _I, _I, _I, ctypes.c_int64, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
 SN_LOSS_MAX_BINS = 16
+SN_QUANTILE_MAX_Q = 8
 SN_OCC_PARTS = 16
 SN_BBOX_PARTS = 32
 SN_METRIC_NCOUNT, SN_METRIC_NVALUE, SN_METRIC_MAX_PARTS = 6, 5, 1024
@@ -1186,6 +1189,64 @@ def param_penalty(P: torch.Tensor, mask: torch.Tensor, weight: float, with_sum: 
                                  int(bool(with_sum)), _ptr(value), _ptr(grad), _stream())
     _check(rc, "sn_param_penalty")
     return value, grad
+
+
+# --------------------------------------------------------------------------- #
+def quantile_parts(n_per: int) -> Tuple[int, int]:
+    """(SN_QUANTILE_PARTS, SN_QUANTILE_BWD_PARTS) of include/scenenet_hip.h."""
+    fwd = 1 if n_per <= 16384 else min(256, (n_per + 16383) // 16384)
+    bwd = 1 if n_per <= 8192 else min(512, (n_per + 8191) // 8192)
+    return fwd, bwd
+
+
+def _quantile_head(pred, gt, qs):
+    if pred.dim() < 2:
+        raise HipLibraryError(f"pred {tuple(pred.shape)} must be [B, Q, ...]")
+    B, Q = int(pred.shape[0]), int(pred.shape[1])
+    n_per = pred.numel() // max(B * Q, 1)
+    if gt.numel() != B * n_per or int(gt.shape[0]) != B:
+        raise HipLibraryError(f"gt {tuple(gt.shape)} must hold one value per voxel of pred {tuple(pred.shape)}: [B, ...]")
+    if len(qs) != Q:
+        raise HipLibraryError(f"pred has {Q} channels for {len(qs)} quantiles")
+    return B, Q, n_per, (ctypes.c_float * max(Q, 1))(*[float(q) for q in qs])
+
+
+@_on_tensor_device
+def quantile_forward(pred: torch.Tensor, gt: torch.Tensor, qs: Sequence[float], ranges: torch.Tensor, bin_w: torch.Tensor):
+    """sn_quantile_forward on pred [B, Q, ...] and gt [B, ...] (one value per voxel).  Returns (loss [1 + Q] f64 = {total,
+    each quantile's share}, loss32 [1 + Q] f32 = the same rounded once, stats [B, Q + H] f64, coef [H] f64)."""
+    B, Q, n_per, qs_c = _quantile_head(pred, gt, qs)
+    H = int(ranges.numel())
+    dev = pred.device
+    ws = torch.empty((B * quantile_parts(n_per)[0] * (Q + H),), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, Q + H), dtype=torch.float64, device=dev)
+    loss = torch.empty((1 + Q,), dtype=torch.float64, device=dev)
+    loss32 = torch.empty((1 + Q,), dtype=torch.float32, device=dev)
+    coef = torch.empty((H,), dtype=torch.float64, device=dev)
+    rc = load().sn_quantile_forward(_ptr(pred, None, "pred"), _DT[pred.dtype], _ptr(gt, None, "gt"), _DT[gt.dtype], B, Q,
+                                    n_per, ctypes.cast(qs_c, c_void_p), _ptr(ranges, torch.float32, "ranges"),
+                                    _ptr(bin_w, torch.float32, "bin_w"), H, _ptr(ws), _ptr(stats), _ptr(loss),
+                                    _ptr(loss32), _ptr(coef), _stream())
+    _check(rc, "sn_quantile_forward")
+    return loss, loss32, stats, coef
+
+
+@_on_tensor_device
+def quantile_backward(pred: torch.Tensor, gt: torch.Tensor, qs: Sequence[float], ranges: torch.Tensor, coef: torch.Tensor,
+                      upstream: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dL/dpred (pred's dtype and shape) from the coefficients of quantile_forward (sn_quantile_backward); upstream: a
+    one-element f64 or f32 tensor (or None = 1)."""
+    B, Q, n_per, qs_c = _quantile_head(pred, gt, qs)
+    grad = torch.empty_like(pred)
+    if upstream is not None and upstream.dtype not in (torch.float64, torch.float32):
+        upstream = upstream.to(torch.float64)
+    up_dt = _DT[upstream.dtype] if upstream is not None else SN_F64
+    rc = load().sn_quantile_backward(_ptr(pred, None, "pred"), _DT[pred.dtype], _ptr(gt, None, "gt"), _DT[gt.dtype], B, Q,
+                                     n_per, ctypes.cast(qs_c, c_void_p), _ptr(ranges, torch.float32, "ranges"),
+                                     int(ranges.numel()), _ptr(coef, torch.float64, "coef"),
+                                     _ptr(upstream, None, "upstream"), up_dt, _ptr(grad), _stream())
+    _check(rc, "sn_quantile_backward")
+    return grad
 
 
 # --------------------------------------------------------------------------- #

@@ -7,6 +7,10 @@ one criterion comes out of ONE streaming pass over (pred, gt) on the GPU (`sn_lo
 the prediction out of a second one (`sn_loss_backward`); sums are fp64 in a fixed order.  The penalties over the ~50
 scalar parameters (cvx_loss, positive_regularizer) are three torch ops on a stacked vector.
 
+QuantileLoss / QuantileGENEOLoss (core/criterions/quant_loss.py) train the quantile ensemble over csrc/quantile.hip: the
+weighted pinball loss of the Q channels in one streaming pass, its gradient in a second.  FocalLoss (focal_loss.py) and
+IoULoss (iou_loss.py) are one pass of csrc/loss.hip each.
+
 There is no CPU path: pred / gt must be HIP tensors.
 """
 from __future__ import annotations
@@ -456,3 +460,154 @@ class GENEO_Tversky_Loss(GENEO_Loss):
     def add_model_specific_args(parent_parser):
         parent_parser = GENEO_Loss.add_model_specific_args(parent_parser)
         return FocalTverskyLoss.add_model_specific_args(parent_parser)
+
+
+class _QuantileLossFn(torch.autograd.Function):
+    """(loss, shares [Q]) of the weighted pinball loss as one differentiable op over sn_quantile_forward /
+    sn_quantile_backward (csrc/quantile.hip); the gradient flows from the loss."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, ranges, bin_w, qs):
+        pred_c, gt_c = pred.contiguous(), gt.contiguous()
+        loss, loss32, _stats, coef = _hip.quantile_forward(pred_c, gt_c, qs, ranges, bin_w)
+        ctx.save_for_backward(pred_c, gt_c, ranges, coef)
+        ctx.qs = qs
+        shares = loss[1:]
+        ctx.mark_non_differentiable(shares)
+        ctx.set_materialize_grads(False)
+        # the kernel writes both roundings: the scalar in pred's dtype is not a cast launch of its own
+        return (loss[0] if pred.dtype == torch.float64 else loss32[0]), shares
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_shares):
+        if g_loss is None:
+            return None, None, None, None, None
+        pred, gt, ranges, coef = ctx.saved_tensors
+        up = g_loss.detach().reshape(1)   # f64 or f32: read as it is
+        return _hip.quantile_backward(pred, gt, ctx.qs, ranges, coef, up), None, None, None, None
+
+
+class QuantileLoss(WeightedMSE):
+    """quant_loss.py:21-102: the pinball loss of Q quantile channels under WeightedMSE's weighting scheme, in the two
+    streaming passes of csrc/quantile.hip.
+
+    The reference's signature, made to work: its constructor hands seven positional arguments to a WeightedMSE.__init__ that
+    takes six and raises a TypeError.  `alpha` is WeightedMSE's weight_alpha, `epsilon` its weight_epsilon, `hist_path` its
+    weighting_scheme_path; `rho` weighs the two penalties of QuantileGENEOLoss (GENEO_Loss's convex_weight).  `gamma` is
+    stored and not used: the reference never reads it in these classes, and the WeightedMSE that took it is not in its tree.
+
+    The loss is PER SAMPLE: mean over the B x voxels elements of weights(y_gt[b]) * sum_i pinball_i(y_gt[b] - y_pred[b, i]).
+    The reference's `y_gt - y_pred[:, i]` broadcasts a [B,1,...] ground truth against [B,...] to [B,B,...] -- every ground
+    truth against every sample's prediction -- and raises for a [B,...] ground truth unless Q = B (its stray
+    `y_gt - y_pred`); at B = 1 it computes exactly this."""
+
+    def __init__(self, targets=None, qs=torch.tensor([0.1, 0.5, 0.9]), hist_path=HIST_PATH, alpha=1, rho=1, epsilon=0.1,
+                 gamma=1, **kwargs) -> None:
+        super().__init__(targets, weighting_scheme_path=hist_path, weight_alpha=alpha, weight_epsilon=epsilon,
+                         convex_weight=rho, **kwargs)
+        qs = torch.as_tensor(qs, dtype=torch.float32).reshape(-1)
+        assert torch.all(qs < 1) and torch.all(qs > 0)  # quantiles in admissible range (quant_loss.py:55)
+        self.cvx_w = rho
+        self.gamma = gamma
+        self.qs = qs.reshape(-1, 1).to(self.device)
+        self._qs = torch.concat((self.qs, self.qs - 1), dim=-1)   # quant_loss.py:58
+        self._qs_host = tuple(float(q) for q in qs.tolist())      # float32 values: what the kernels take by value
+        self.last_quantile_terms = None
+
+    def data_fidelity(self, y_pred: torch.Tensor, y_gt: torch.Tensor):
+        return y_gt - y_pred
+
+    def quantile_loss(self, y_pred: torch.Tensor, y_gt: torch.Tensor):
+        """quant_loss.py:74-89, per sample: the unweighted sum over the quantiles of the pinball loss of every voxel,
+        [B, ...], in torch ops on the device."""
+        if not y_pred.is_cuda:
+            raise _hip.HipLibraryError("QuantileLoss runs on the HIP device only (no CPU path): move y_pred to cuda")
+        gt = y_gt.reshape((y_pred.shape[0],) + tuple(y_pred.shape[2:]))
+        if not gt.dtype.is_floating_point:
+            gt = gt.to(y_pred.dtype)
+        qs = self.qs.to(y_pred.device)
+        q_loss = []
+        for i in range(qs.shape[0]):
+            d_fid = self.data_fidelity(y_pred[:, i], gt)
+            q_loss.append(torch.max(qs[i] * d_fid, (qs[i] - 1) * d_fid).unsqueeze(dim=1))
+        return torch.sum(torch.cat(q_loss, dim=1), dim=1)
+
+    def forward(self, y_pred: torch.Tensor, y_gt: torch.Tensor):
+        """quant_loss.py:92-102, per sample.  y_pred [B, Q, ...]; y_gt [B, 1, ...] or [B, ...].  A scalar in y_pred's
+        dtype; `last_quantile_terms` then holds each quantile's share of it ([Q] f64, detached, no synchronisation)."""
+        if not y_pred.is_cuda or not y_gt.is_cuda:
+            raise _hip.HipLibraryError("QuantileLoss runs on the HIP device only (no CPU path): move y_pred / y_gt to cuda")
+        if y_pred.dim() < 2 or y_pred.shape[1] != len(self._qs_host):
+            raise ValueError(f"y_pred {tuple(y_pred.shape)} must be [B, {len(self._qs_host)}, ...]")
+        if y_gt.numel() * y_pred.shape[1] != y_pred.numel() or y_gt.shape[0] != y_pred.shape[0]:
+            raise ValueError(f"y_gt {tuple(y_gt.shape)} must be [B, 1, ...] or [B, ...] of y_pred {tuple(y_pred.shape)}")
+        ranges, bin_w = self._device_tables(y_pred.device)
+        loss, shares = _QuantileLossFn.apply(y_pred, y_gt, ranges, bin_w, self._qs_host)
+        self.last_quantile_terms = shares
+        return loss
+
+
+class QuantileGENEOLoss(QuantileLoss, GENEO_Loss):
+    """quant_loss.py:105-142: QuantileLoss + the penalties of GENEO_Loss summed over the ensemble's nets."""
+
+    def __init__(self, targets=None, qs=torch.tensor([0.1, 0.5, 0.9]), hist_path=HIST_PATH, alpha=1, rho=1, epsilon=0.1,
+                 gamma=1, **kwargs) -> None:
+        super().__init__(targets, qs, hist_path, alpha, rho, epsilon, gamma, **kwargs)
+
+    def cvx_loss(self, cvx_coeffs: list):
+        return sum(GENEO_Loss.cvx_loss(self, cvx_c) for cvx_c in cvx_coeffs)
+
+    def positive_regularizer(self, params: list):
+        return sum(GENEO_Loss.positive_regularizer(self, g_params) for g_params in params)
+
+    def forward(self, y_pred, y_gt, cvx_coeffs: list, geneo_params: list):
+        """y_pred, y_gt as QuantileLoss.forward; cvx_coeffs / geneo_params: what SCENENetQuantile.get_cvx_coefficients() /
+        get_geneo_params() return (one ParameterDict per net)."""
+        data_fidelity = QuantileLoss.forward(self, y_pred, y_gt)
+        return data_fidelity + self.cvx_loss(cvx_coeffs) + self.positive_regularizer(geneo_params)
+
+
+class FocalLoss(torch.nn.Module):
+    """focal_loss.py:8-43: alpha * (1 - exp(-BCE))^gamma * BCE.  'mean' / 'sum': the BCE is a scalar -- K5's weighted-BCE
+    pass on the unit tables ('sum' = mean x numel) -- followed by three scalar torch ops; 'none': the expression in torch
+    ops on the device."""
+
+    def __init__(self, reduction="mean", alpha=0.5, gamma=2):
+        super().__init__()
+        self.reduction = reduction
+        self.focal_alpha = alpha
+        self.focal_gamma = gamma
+
+    def forward(self, inputs, targets):
+        if not inputs.is_cuda:
+            raise _hip.HipLibraryError("FocalLoss runs on the HIP device only (no CPU path): move inputs to cuda")
+        inputs, targets = inputs.reshape(-1), targets.reshape(-1)
+        if self.reduction in ("mean", "sum"):
+            ranges, bin_w = _unit_tables(inputs.device)
+            bce = _dense_loss(inputs, targets, ranges, bin_w, _hip.SN_LOSS_WBCE)
+            if self.reduction == "sum":
+                bce = bce * inputs.numel()
+        else:   # 'none' (an unknown reduction raises in torch, like the reference)
+            tgt = targets if targets.dtype.is_floating_point else targets.to(inputs.dtype)
+            bce = torch.nn.functional.binary_cross_entropy(inputs, tgt, reduction=self.reduction)
+        return self.focal_alpha * (1 - torch.exp(-bce)) ** self.focal_gamma * bce
+
+    @staticmethod
+    def add_model_specific_args(parent_parser):
+        parser = parent_parser.add_argument_group("FocalLoss")
+        parser.add_argument("--focal_alpha", type=float, default=0.5)
+        parser.add_argument("--focal_gamma", type=float, default=2)
+        return parent_parser
+
+
+class IoULoss(torch.nn.Module):
+    """iou_loss.py:7-25: 1 - (sum(p t) + smooth) / (sum(p) + sum(t) - sum(p t) + smooth) over the whole batch.  TP + FP + FN
+    = sum(p) + sum(t) - sum(p t), so this is K5's Tversky term with alpha = beta = 1, gamma = 1: one pass."""
+
+    def __init__(self, weight=None, size_average=True):
+        super().__init__()
+
+    def forward(self, inputs, targets, smooth=1):
+        ranges, bin_w = _unit_tables(inputs.device)
+        return _dense_loss(inputs, targets, ranges, bin_w, _hip.SN_LOSS_FOCAL_TVERSKY, tversky_alpha=1, tversky_beta=1,
+                           focal_gamma=1.0, tversky_smooth=smooth)

@@ -9,60 +9,15 @@
 // written.  All accumulation is fp64 in a fixed order (per-thread strided, wave shuffle tree, waves in order, parts
 // in order), so a loss value is bit-reproducible.
 #include "common.h"
-#include <type_traits>
+#include "loss_common.h"   // Vec4 / load4 / store4, BinOf, bin_lookup, wave_sum, kMaxBins: shared with quantile.hip (K20)
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxBins = SN_LOSS_MAX_BINS;
 
 using bf16 = __bf16;   // SN_BF16: storage only -- every value is widened to fp32 before it is used
 template <typename T> struct ComputeOf { using type = T; };
 template <> struct ComputeOf<bf16> { using type = float; };
-
-template <typename T>
-struct Vec4 {
-    T v[4];
-};
-
-template <typename T>
-__device__ __forceinline__ Vec4<T> load4(const T* p) {
-    Vec4<T> r;
-    if constexpr (sizeof(T) == 2) {
-        const uint2 u = *reinterpret_cast<const uint2*>(p);
-        __builtin_memcpy(&r, &u, 8);
-    } else if constexpr (sizeof(T) == 4) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        __builtin_memcpy(&r, &u, 16);
-    } else if constexpr (sizeof(T) == 8) {
-        const uint4 u0 = reinterpret_cast<const uint4*>(p)[0], u1 = reinterpret_cast<const uint4*>(p)[1];
-        __builtin_memcpy(&r.v[0], &u0, 16);
-        __builtin_memcpy(&r.v[2], &u1, 16);
-    } else {
-        const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
-        __builtin_memcpy(&r, &u, 4);
-    }
-    return r;
-}
-
-template <typename T>
-__device__ __forceinline__ void store4(T* p, const Vec4<T>& r) {
-    if constexpr (sizeof(T) == 2) {
-        uint2 u;
-        __builtin_memcpy(&u, &r, 8);
-        *reinterpret_cast<uint2*>(p) = u;
-    } else if constexpr (sizeof(T) == 4) {
-        uint4 u;
-        __builtin_memcpy(&u, &r, 16);
-        *reinterpret_cast<uint4*>(p) = u;
-    } else {
-        uint4 u0, u1;
-        __builtin_memcpy(&u0, &r.v[0], 16);
-        __builtin_memcpy(&u1, &r.v[2], 16);
-        reinterpret_cast<uint4*>(p)[0] = u0;
-        reinterpret_cast<uint4*>(p)[1] = u1;
-    }
-}
 
 // max(log(v), -100) as torch's binary_cross_entropy clamps it, in pred's dtype
 template <typename T>
@@ -71,51 +26,12 @@ __device__ __forceinline__ T bce_log(T v) {
     else return fmaxf(logf(v), -100.0f);
 }
 
-// w_mse.py:122 -- argmin_k |y - ranges[k]|, first minimum; arithmetic in gt's dtype promoted with the fp32 ranges
-// (f64 gt: fp64; f32 gt: fp32; byte gt, our extension: fp32).
-template <typename GT>
-struct BinOf {
-    using C = typename std::conditional<std::is_same<GT, double>::value, double, float>::type;
-    C r[kMaxBins];
-    int H;
-    __device__ void init(const float* ranges, int h) {
-        H = h;
-#pragma unroll
-        for (int k = 0; k < kMaxBins; ++k) r[k] = (C)ranges[k < h ? k : h - 1];
-    }
-    __device__ __forceinline__ int operator()(GT y) const {
-        const C yy = (C)y;
-        C best = fabs(yy - r[0]);
-        int idx = 0;
-#pragma unroll
-        for (int k = 1; k < kMaxBins; ++k) {
-            const C d = fabs(yy - r[k]);
-            const bool lt = (k < H) && (d < best);
-            best = lt ? d : best;
-            idx = lt ? k : idx;
-        }
-        return idx;
-    }
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------- pass 1: partial statistics
 // grid = (parts, B); block `part` owns elements [part*span, (part+1)*span) of sample b (span a multiple of 4).
 // kBinary (gt is SN_OCC8, values in {0,1}): two classes, everything in registers (~10 VALU per element).
 // Otherwise: per-thread per-bin accumulators live in LDS ([bin][thread], conflict free) -- register accumulators
 // would cost a 16-way select per element and make the pass VALU-bound; byte targets find their bin in a 256-entry
-// LDS table, float targets by the first-minimum search of the reference.
-template <typename GT>
-__device__ __forceinline__ int bin_lookup(const BinOf<GT>& bin, const int* lut, GT tv) {
-    if constexpr (sizeof(GT) == 1) return lut[tv];
-    else return bin(tv);
-}
-
+// LDS table, float targets by the first-minimum search of the reference (bin_lookup, loss_common.h).
 template <typename PT, typename GT, bool kBinary>
 __global__ __launch_bounds__(kThreads) void loss_stats_kernel(const PT* __restrict__ pred, const GT* __restrict__ gt,
                                                               long n_per, long span, const float* __restrict__ ranges,
