@@ -135,6 +135,12 @@ int sn_device_count(void);
  *   "conv_i8z_inject_fault" (switch, default 0): TEST HOOK.  1 = the next z-walk launches never report plane 0's first raw
  *       rows as landed, so a dependency spin gives up (~0.5 s per launch): the way to see the loud failure path -- NaN
  *       outputs and the sticky device status -- on the product build (tests/test_gpu_conv_zwalk.py).
+ *   "conv_i8z_segments" (0 .. 4, default 0): how the skipping z-walk cuts its columns in z.  1 = whole columns unless they do
+ *       not fill the chip (the dense walk's plan); n >= 2 = n segments per column, segment sg of column xt dealt to the
+ *       workgroup of column xt + sg max(1, nxt / n), where the shape allows it (a segment has at least 8 planes); on a head-only
+ *       launch a workgroup then checks its own jobs, fills those whose operand region holds no set voxel without walking them
+ *       and walks the rest.  0 = two such segments on head-only launches with Z >= 32 and at least two columns in x that the
+ *       dense plan would walk as whole columns, else that plan.  Same results bit for bit; ignored under "conv_i8z_dense".
  *   "conv_i8z_dense" (switch, default 0): the z-walk (sn_conv_bank_prepared[_served]) skips every round whose operand
  *       window -- 9 planes x 9 halo rows -- holds no set voxel and stores the epilogue's constant instead; the results are
  *       the same bit for bit (banks with a non-finite coefficient are never skipped), the run time depends on the data.

@@ -272,8 +272,8 @@ def conv_i8_spin_timeouts() -> int:
 
 def conv_i8z_round_counts() -> Tuple[int, int]:
     """(rounds run, rounds skipped) by the z-walk contraction since the library was loaded, on the current device: a round
-    whose operand window holds no set voxel is skipped unless option conv_i8z_dense is 1; synchronises
-    (sn_conv_i8z_round_counts)."""
+    whose operand window holds no set voxel is skipped unless option conv_i8z_dense is 1, and so is every round of a z segment
+    that a workgroup filled without walking it (option conv_i8z_segments); synchronises (sn_conv_i8z_round_counts)."""
     buf = (ctypes.c_ulonglong * 2)()
     _check(load().sn_conv_i8z_round_counts(ctypes.cast(buf, ctypes.c_void_p)), "sn_conv_i8z_round_counts")
     return int(buf[0]), int(buf[1])

@@ -45,6 +45,7 @@ enum Opt {
     kOptCorrDense,
     kOptCorrSparseTileBytes,
     kOptConvI8zInjectFault,
+    kOptConvI8zSegments,
     kOptConvI8zDense,
     kOptCount
 };

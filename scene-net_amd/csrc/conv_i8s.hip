@@ -334,6 +334,20 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
         best_seg = SN_I8Z_SKIP_NSEG;
         z.deal = 1;
         z.deal_shift = SN_I8Z_SKIP_SHIFT;
+    } else if (!z.dense) {
+        // sn_set_option("conv_i8z_segments"): 1 = the plan above; n >= 2 = n z segments per column, segment sg of column xt
+        // dealt to the workgroup of column xt + sg max(1, nxt / n) -- a column's parts go as far apart in x as the tile allows,
+        // and heavy things are local in x; 0 = two dealt segments where the launch is the head-only one (a workgroup drops
+        // its dead jobs: conv_i8z.inc, DEAD JOBS), the tile has two columns in x to deal over, a half is at least the ring
+        // (Z >= 32) and the search above found nothing better than whole columns.
+        const int want = sn::option(sn::kOptConvI8zSegments);
+        const int n = want >= 2 ? want : (want == 0 && !act && z.nxt >= 2 && Z >= 32 && best_seg == 1) ? 2 : 0;
+        if (n >= 2 && n <= max_seg && (ncol * n + cus - 1) / cus <= kZMaxJobs) {
+            best_seg = n;
+            z.deal = 1;
+            z.deal_shift = z.nxt / n > 1 ? z.nxt / n : 1;
+            z.fill_dead = act ? 0 : 1;
+        }
     }
     z.LZ = (Z + best_seg - 1) / best_seg;
     z.nseg = (Z + z.LZ - 1) / z.LZ;

@@ -71,6 +71,12 @@
 // base; under head & 1 the load-add-activate of zero_round1 / zero_round2 stays.  The per-round verdicts, the table reads and
 // the ring addresses are formed only for a ticket that runs a round.  The activations form (kAct) keeps the round-6 ticket:
 // see kLean in the kernel.
+//
+// DEAD JOBS (round 8, head-only form).  The launch ends with its busiest columns.  Under the dealt plan (ZShape::deal, fill_dead:
+// sn_set_option("conv_i8z_segments"), conv_i8s.hip) a column is cut into z segments that go to different workgroups, and a
+// workgroup checks its own jobs in its prologue: one whose whole operand region holds no set voxel is not streamed at all -- its
+// outputs are filled with what its rounds would have stored and its rounds counted as skipped -- and the ticket loop walks the
+// live jobs only.  No extra launch, nothing shared between workgroups, nothing in the ticket loop: see DEAD JOBS in the kernel.
 
 constexpr int kZTX = 8;                        // output x-rows per column
 constexpr int kZRows = kZTX + 8;               // halo rows per plane
@@ -124,6 +130,9 @@ struct ZShape {
     int32_t* route;
     int served;                   // the caller left the fallback launch out (sn_conv_bank_prepared_served): a walk that declines
                                   // must not return quietly -- it poisons its outputs and latches the sticky status
+    int fill_dead;                // head-only form, dealt plan: a workgroup drops the jobs whose operand region holds no set voxel
+                                  // from its stream and fills their outputs in its prologue (DEAD JOBS).  (In what was padding:
+                                  // no other field moves, the activations form's argument loads stay as they were.)
     int32_t* sticky;              // the device's sticky status words (host-pinned, cabi.hip: sn::sticky_device_ptr)
     int dbg;
     int dense;                    // sn_set_option("conv_i8z_dense"): run every round, whatever its window holds
@@ -403,7 +412,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     // counters: [0..15] folded[slot]: fold passes of the planes that lived there (4 per plane);
     //           [16..31] read[slot]: tickets of the slots s = slot (mod 16) that are through with their ring reads (kTPS per slot);
     //           [32..95] landed[pass][slot]: LDS-DMA passes arrived;  [96] ticket counter;  [97] asymmetric bank;  [98] a spin gave up
-    //           [99] can_skip;  [100] rounds run, [101] rounds skipped, [102] waves that have added theirs
+    //           [99] can_skip;  [100] rounds run, [101] rounds skipped, [102] waves that have added theirs;  [103] live jobs (DEAD JOBS)
     int* const ticket_ctr = cnt + 96;
 
 #ifdef SN_CONV_TIMING
@@ -417,9 +426,22 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     SN_ST(0);
     const size_t V = (size_t)zs.Z * zs.X * zs.Y;
     const int grid = (int)gridDim.x;
-    const int my_jobs = (int)blockIdx.x < zs.njobs ? (zs.njobs - 1 - (int)blockIdx.x) / grid + 1 : 0;
-    const int NPL = my_jobs * zs.PL;          // planes of this workgroup's stream
-    const int nslots = NPL + kZD;             // slots (the last kZD only flush rounds)
+    const int dealt = (int)blockIdx.x < zs.njobs ? (zs.njobs - 1 - (int)blockIdx.x) / grid + 1 : 0;   // jobs of this workgroup
+    int my_jobs = dealt;                      // ... and those it walks (DEAD JOBS below: the live ones)
+    int NPL = my_jobs * zs.PL;                // planes of this workgroup's stream
+    int nslots = NPL + kZD;                   // slots (the last kZD only flush rounds)
+    // DEAD JOBS (round 8, head-only form, zs.fill_dead: the dealt plan).  A job is DEAD when no byte of x[b] is set in planes
+    // zs - 4 .. zs + LZ + 3, rows x0 - 4 .. x0 + 11, y0 - 4 .. y0 + 67 (clipped to the grid): the union of the windows of all its
+    // rounds under the conservative row rule above, so every one of its rounds would be skipped.  The workgroup checks its own
+    // jobs in its prologue (16-byte loads of the rows' pieces -- the LDS-DMA's pieces -- ahead of the blob copy), moves
+    // the live ones to the front of its job table, requests the first planes of the first LIVE job only then, and fills a dead
+    // job's outputs with what its rounds would have stored (the lean ticket's constant, or zero_round's load-add-activate under
+    // head & 1) with 16-byte stores.  A launch that declines, or may not skip (can_skip), treats every job as live.  Nothing of
+    // the ticket loop knows: it walks a shorter stream.  A workgroup whose FIRST job is live -- it stays the first whatever the
+    // launch decides -- requests that job's planes as soon as the flags are known, so its LDS-DMA flies through the verdict as
+    // the parent's does.  The job flags live in the folded ring, which nothing uses before the first fold pass.
+    const bool fill_dead = kLean && zs.fill_dead != 0;
+    int* const live = reinterpret_cast<int*>(Yq);   // [kZMaxJobs], fill_dead only
     if (tid < 128) cnt[tid] = 0;
     if (tid >= 128 && tid < 192) {
         // lane roles of a ticket's dependency check (one LDS read of counter `idx`, expected value `expect`):
@@ -478,6 +500,10 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             sg = j % zs.nseg; j /= zs.nseg;
         }
         jobtab[tid] = make_int4(j, xt * kZTX, yt * TY, sg * zs.LZ);
+    }
+    if constexpr (kLean) {
+        if (fill_dead)
+            for (int i = tid; i < kZMaxJobs; i += kNT) live[i] = 0;
     }
     lds_barrier();
 
@@ -548,7 +574,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     // ---- NaN over everything this workgroup owns in `out` / `act` (cold: a spin gave up, or a `served` launch declined)
     auto poison_jobs = [&]() {
         const OT nan = (OT)__int_as_float(0x7fc00000);
-        for (int k = 0; k < my_jobs; ++k) {
+        for (int k = 0; k < dealt; ++k) {   // (every job the workgroup was dealt: walked or filled)
             const int4 jb = jobtab[k];
             for (int r = wave; r < zs.LZ * kZTX; r += kW) {
                 const int gz = jb.w + (r >> 3), gx = jb.y + (r & 7), gy = jb.z + lane;
@@ -562,8 +588,67 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     };
 
     // ---- prologue: the first planes' raw rows are requested before anything else; the blob is copied while they fly
-    const int npre = NPL < kZPre ? NPL : kZPre;
-    for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
+    // (fill_dead: the planes are requested once the first live job is known, below; here the check's loads go out instead)
+    int npre = NPL < kZPre ? NPL : kZPre;
+    if (!fill_dead)
+        for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
+    // DEAD JOBS, the check: OR of the bytes of the operand regions of jobs k0 and k0 + 1 that this thread reads.  A thread keeps
+    // one (row, piece) of the region -- kNT is a multiple of 128 = 16 rows x 8 piece slots, 6 of them pieces -- and takes every
+    // (kNT / 128)-th plane; the pieces are the LDS-DMA's (16 bytes from y0 - 16 on, wholly inside or outside the grid), of which
+    // the first and the last count with 4 bytes (y0 - 4 .., .. y0 + 67).  Whatever lies outside the grid or the region is read
+    // again from the start of the tile and dropped: every load is unconditional, a batch of 2 x 8 is in flight at once.
+    auto region_or2 = [&](int k0, uint32_t& a0, uint32_t& a1) {
+        static_assert(kNT % 128 == 0, "a thread's (row, piece) is the same for every plane it takes");
+        constexpr int kStep = kNT / 128, kBatch = 8;
+        const int pc = tid & 7, row = (tid >> 3) & 15;
+        const bool two = k0 + 1 < dealt;
+        const int4 j0 = jobtab[k0], j1 = jobtab[two ? k0 + 1 : k0];
+        // (the thread's row and piece inside the grid?  its byte offset in plane 0 of the tile, and which dwords count)
+        const int gx0 = j0.y - 4 + row, gy0 = j0.z - PYA + 16 * pc, gx1 = j1.y - 4 + row, gy1 = j1.z - PYA + 16 * pc;
+        const bool in0 = pc < kRowPieces && (unsigned)gx0 < (unsigned)zs.X && (unsigned)gy0 < (unsigned)zs.Y;
+        const bool in1 = two && pc < kRowPieces && (unsigned)gx1 < (unsigned)zs.X && (unsigned)gy1 < (unsigned)zs.Y;
+        const int plane = zs.X * zs.Y;
+        const uint8_t* const t0 = x + (size_t)j0.x * V + (unsigned)(in0 ? gx0 * zs.Y + gy0 : 0);
+        const uint8_t* const t1 = x + (size_t)j1.x * V + (unsigned)(in1 ? gx1 * zs.Y + gy1 : 0);
+        const uint32_t kx = pc == kRowPieces - 1 ? ~0u : pc == 0 ? 0u : ~0u, kyz = (pc == 0 || pc == kRowPieces - 1) ? 0u : ~0u,
+                       kw = pc == 0 ? ~0u : pc == kRowPieces - 1 ? 0u : ~0u;
+#pragma unroll 1
+        for (int pl0 = tid >> 7; pl0 < zs.PL; pl0 += kStep * kBatch) {
+            // a plane outside the region or the grid: the thread reads plane 0 of its tile again and drops what it gets
+            uint4 v0[kBatch], v1[kBatch];
+            bool ok0[kBatch], ok1[kBatch];
+#pragma unroll
+            for (int u = 0; u < kBatch; ++u) {
+                const int pl = pl0 + u * kStep, gz0 = j0.w - 4 + pl, gz1 = j1.w - 4 + pl;
+                ok0[u] = in0 && pl < zs.PL && (unsigned)gz0 < (unsigned)zs.Z;
+                ok1[u] = in1 && pl < zs.PL && (unsigned)gz1 < (unsigned)zs.Z;
+                v0[u] = *reinterpret_cast<const uint4*>(t0 + (unsigned)(ok0[u] ? gz0 * plane : 0));
+                v1[u] = *reinterpret_cast<const uint4*>(t1 + (unsigned)(ok1[u] ? gz1 * plane : 0));
+            }
+#pragma unroll
+            for (int u = 0; u < kBatch; ++u) {
+                const uint32_t w0 = (v0[u].x & kx) | ((v0[u].y | v0[u].z) & kyz) | (v0[u].w & kw);
+                const uint32_t w1 = (v1[u].x & kx) | ((v1[u].y | v1[u].z) & kyz) | (v1[u].w & kw);
+                a0 |= ok0[u] ? w0 : 0u;
+                a1 |= ok1[u] ? w1 : 0u;
+            }
+        }
+    };
+    // (one ballot per wave, then one lane sets the job's flag: every writer stores the same 1, an OR without the atomic)
+    auto region_report = [&](int k, uint32_t a) {
+        if (__builtin_amdgcn_ballot_w64(a != 0u) != 0ull && lane == 0) live[k] = 1;
+    };
+    if constexpr (kLean) {
+        if (fill_dead) {
+#pragma unroll 1
+            for (int k = 0; k < dealt; k += 2) {   // (more than two jobs per workgroup: one more latency per pair)
+                uint32_t a0 = 0u, a1 = 0u;
+                region_or2(k, a0, a1);
+                region_report(k, a0);
+                region_report(k + 1, a1);
+            }
+        }
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(prep + kPrepWd);
         for (int i = tid; i < kFoldSteps * 3 * 64; i += kNT) Wd[i] = src[i];
@@ -581,6 +666,13 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         if (tid >= 64 && tid < 128) cnt[32 + tid - 64] = (((tid - 64) & 15) < npre && !((zs.dbg & 1) && tid == 64)) ? 1 : 0;
     }
     lds_barrier();
+    bool early = false;   // fill_dead: the first planes are in flight already (job 0 is live and owns all of them)
+    if constexpr (kLean) {
+        if (fill_dead && dealt > 0 && zs.PL >= kZPre && __builtin_amdgcn_readfirstlane(live[0]) != 0) {
+            early = true;   // (npre = kZPre: landed[] above is the stream's, whatever becomes of the other jobs)
+            for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
+        }
+    }
     {
         // the launch's verdict, for the combined fallback launch enqueued behind this one (conv_i8_fallback_kernel):
         //   0 served here;  1 quantisation bound over the tolerance: the fp32 form;  2 bank not symmetric in x and y: the
@@ -618,12 +710,109 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         // can_skip: an empty round's epilogue is a constant only if coefficient x 0 = + 0 for every coefficient
         const bool all_fin = __builtin_amdgcn_ballot_w64(!fin) == 0ull;
         if (lane == 0) cnt[99] = (all_fin && !zs.dense) ? 1 : 0;
+        if constexpr (kLean) {
+            if (fill_dead) {
+                // DEAD JOBS, the job table: live jobs first, in their order, the dead ones behind them, written by this wave from a copy
+                // it made (a wave's DS operations execute in order).  A launch that may not skip has no dead job.
+                const bool may_skip = all_fin && !zs.dense;
+                int4* const old = reinterpret_cast<int4*>(Yq + kZMaxJobs * 4);   // a copy of the table, behind the flags
+                int nlive = 0;
+#pragma unroll 1
+                for (int k0 = 0; k0 < dealt; k0 += 64) {
+                    const int k = k0 + lane;
+                    const bool lv = k < dealt && (!may_skip || live[k] != 0);
+                    if (k < dealt) {
+                        old[k] = jobtab[k];
+                        live[k] = lv ? 1 : 0;
+                    }
+                    nlive += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lv));
+                }
+                int at_live = 0, at_dead = nlive;
+#pragma unroll 1
+                for (int k0 = 0; k0 < dealt; k0 += 64) {
+                    const int k = k0 + lane;
+                    const bool in = k < dealt, lv = in && live[k] != 0;
+                    const unsigned long long ml = __builtin_amdgcn_ballot_w64(lv), md = __builtin_amdgcn_ballot_w64(in && !lv);
+                    const unsigned long long m = lv ? ml : md;
+                    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (in) jobtab[(lv ? at_live : at_dead) + rank] = old[k];
+                    at_live += __builtin_popcountll(ml);
+                    at_dead += __builtin_popcountll(md);
+                }
+                if (lane == 0) cnt[103] = nlive;
+            }
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (my_jobs == 0) return;
     const bool can_skip = __builtin_amdgcn_readfirstlane(cnt[99]) != 0;
     int n_run = 0, n_skip = 0;   // this wave's rounds (scalar)
+    if constexpr (kLean) {
+        if (fill_dead) {
+            // DEAD JOBS: the stream is the live jobs'.  Unless they are in flight already, its first planes are requested now,
+            // and the dead jobs are filled while they fly.
+            my_jobs = __builtin_amdgcn_readfirstlane(cnt[103]);
+            NPL = my_jobs * zs.PL;
+            nslots = NPL + kZD;
+            if (!early) {
+                npre = NPL < kZPre ? NPL : kZPre;
+                for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
+                if (tid >= 64 && tid < 128) cnt[32 + tid - 64] = (((tid - 64) & 15) < npre && !((zs.dbg & 1) && tid == 64)) ? 1 : 0;
+            }
+            // what a dead job's rounds would have stored, four values per thread and store: zero_round1 / zero_round2's
+            // operations from e = + 0.0 on (the zero made opaque so that they are issued), for the rows and planes inside the grid
+            int dead_rounds = 0;
+#pragma unroll 1
+            for (int k = my_jobs; k < dealt; ++k) {
+                const int4 jb = jobtab[k];
+                const int nz = zs.Z - jb.w < zs.LZ ? zs.Z - jb.w : zs.LZ;
+                const int nx = zs.X - jb.y < kZTX ? zs.X - jb.y : kZTX;
+                const int ny4 = (zs.Y - jb.z < TY ? zs.Y - jb.z : TY) >> 2;
+                dead_rounds += nz * ((nx + kH - 1) / kH);
+                if (!out) continue;
+                OT* const tile = out + (size_t)jb.x * V;
+#pragma unroll 1
+                for (int i = tid; i < nz * (kZTX * 16); i += kNT) {
+                    const int yq = i & 15, xr = (i >> 4) & (kZTX - 1), pz = i >> 7;
+                    if (yq >= ny4 || xr >= nx) continue;
+                    OT* const o = tile + (unsigned)(((jb.w + pz) * zs.X + jb.y + xr) * zs.Y + jb.z + 4 * yq);
+                    float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+                    if (zs.head & 1) {
+                        if constexpr (sizeof(OT) == 4) {
+                            const float4 v = *reinterpret_cast<const float4*>(o);
+                            t[0] += v.x; t[1] += v.y; t[2] += v.z; t[3] += v.w;
+                        } else {
+                            const double2 v = reinterpret_cast<const double2*>(o)[0], w = reinterpret_cast<const double2*>(o)[1];
+                            t[0] += (float)v.x; t[1] += (float)v.y; t[2] += (float)w.x; t[3] += (float)w.y;
+                        }
+                    }
+                    if (zs.head & 2) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) t[e] = relu_tanh(t[e]);
+                    }
+                    if constexpr (sizeof(OT) == 4) {
+                        *reinterpret_cast<float4*>(o) = make_float4(t[0], t[1], t[2], t[3]);
+                    } else {
+                        reinterpret_cast<double2*>(o)[0] = make_double2((double)t[0], (double)t[1]);
+                        reinterpret_cast<double2*>(o)[1] = make_double2((double)t[2], (double)t[3]);
+                    }
+                }
+            }
+            if (my_jobs == 0) {
+                // no live job: the workgroup has filled everything it was dealt and requested nothing (npre = 0); its rounds
+                // go to the device's count directly
+                if (tid == 0) atomicAdd(&g_zwalk_rounds[1], (unsigned long long)(unsigned)dead_rounds);
+                return;
+            }
+            if (wave == 0) n_skip = dead_rounds;
+            if (!early) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the first planes have landed: landed[] above says so)
+                __syncthreads();
+            }
+        }
+    }
     SN_ST(4);
 
     bool healthy = true;
