@@ -33,13 +33,15 @@ FLAGS_thin := -ffp-contract=off
 FLAGS_voxel_classes := -ffp-contract=off
 # scan_merge.hip: K9's membership test and K1's binning (regions.h, binning.h) and the interior depth, every fp64 operation rounded once
 FLAGS_scan_merge := -ffp-contract=off
+# knn.hip: a squared distance is (dx*dx + dy*dy) + dz*dz and a mean a sum of square roots over a count, every fp64 operation rounded once
+FLAGS_knn := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so
 
-$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h $(SRC)/binning.h $(SRC)/scan.h $(SRC)/regions.h $(SRC)/loss_common.h
+$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h $(SRC)/binning.h $(SRC)/scan.h $(SRC)/regions.h $(SRC)/loss_common.h $(SRC)/cell_grid.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(CXXFLAGS) $(FLAGS_$*) -c $< -o $@
 

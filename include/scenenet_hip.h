@@ -1486,6 +1486,87 @@ int sn_scan_merge(const void* grid, int dtype, int channels, int B, int nx, int 
                   sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K21 -- nearest neighbours: the k smallest neighbour distances of every point within a radius, on K10's cell grid.
+ * replaces: avg_dist_points (utils/pcd_processing.py:477-505: a Python loop over all pairs with np.linalg.norm whose list
+ *           of distances is sorted again for every point) -- the reference's only question about the spacing of a cloud;
+ *           and is the primitive under the k-distance curve (choosing eps / min_points), point spacing (choosing a voxel
+ *           size or a thinning rate) and statistical / radius outlier removal.
+ *
+ * batch:     pts [total,3] f64 with offsets [B+1] i64 on the DEVICE -- the ragged CSR layout of K1 and K17, offsets[0] = 0
+ *            and offsets[B] <= total; B = 1 is a whole scan.  Empty tiles are legal.
+ * candidate: for row p of tile b, a row q != p (by row index) OF THE SAME TILE with d2 = (dx*dx + dy*dy) + dz*dz <=
+ *            radius*radius in fp64, in exactly this form, each product and sum rounded once and never contracted, the
+ *            comparison literal: a row with a NaN or infinite coordinate has no candidates and is nobody's candidate.
+ *            With SN_KNN_EXCLUDE_ZERO candidates with d2 == 0 are left out (the reference's `if euc > 0`: duplicates go
+ *            with the point itself).
+ * outputs, indexed by the row's own index in the packed array (scan order):
+ *   d2        [total,k] f64: the k smallest candidate d2, ascending; +inf in the columns beyond the candidates
+ *   found     [total] i32: the number of candidates within the radius -- ALL of them, not capped at k
+ *   mean_dist [total] f64 (nullable): (sqrt(d2[0]) + sqrt(d2[1]) + ...) / c over the c = min(found, k) finite columns,
+ *             added in ascending column order, every operation rounded once (sqrt correctly rounded); NaN where found == 0
+ *   index     [total,k] i64 (nullable): the packed row indices of those neighbours, -1 beyond min(found, k)
+ *   The k are chosen by the lexicographic order (d2, row index): ties do not depend on the order of rows inside a cell.
+ *   A row at or beyond offsets[B] belongs to no tile: found 0, +inf, NaN, -1.
+ * Every result is a function of the candidate set alone; nothing depends on scheduling.
+ * grid:      K10's, an accelerator only: cubic cells of side mult * radius * (1 + 2^-20) -- derived HERE from radius and the
+ *            integer mult >= 1, so no caller can hand in a side that breaks the 27-cell claim -- laid from tile b's own
+ *            lo [B,3] f64 (device), dims (dim_x, dim_y, dim_z) host integers shared by all tiles, the cell key tile *
+ *            cells_per_tile + local cell (tiles never see each other, whatever coordinates they share), B * dim_x * dim_y
+ *            * dim_z <= 2^22.  sn_dbscan_cell_grid computes dims and the side (mult = side / (radius * (1 + 2^-20))) for
+ *            an extent and a cell budget.  A point outside its tile's grid is clamped into an edge cell: the result is
+ *            exact for ANY finite lo and any dims >= 1; they decide the speed only.  dims (1, 1, 1) is brute force.
+ * statistics (sn_knn_tile_stats): stats [B, SN_KNN_NSTAT] f64 per tile = n_valid (rows with found >= 1), n_full (rows
+ *            with found >= k), sum and sum of squares (each square rounded once) of mean_dist over the valid rows, and
+ *            their max (-inf for a tile without a valid row).  Fixed order: partials per chunk of
+ *            sn_knn_chunk_points() consecutive rows of a tile, then one combining pass per tile in chunk order; no
+ *            floating-point atomics: two runs on the same input give the same bits.
+ * ------------------------------------------------------------------------- */
+#define SN_KNN_MAX_K 16
+#define SN_KNN_NSTAT 5         /* n_valid, n_full, sum, sum_sq, max */
+#define SN_KNN_LAUNCHES 4      /* cells, prefix, scatter, search */
+#define SN_KNN_EXCLUDE_ZERO 1  /* flags */
+
+/* Rows per workgroup of the kernels and per partial of the statistics (256): host only -- lets a test put its sizes on
+ * the seams. */
+int sn_knn_chunk_points(void);
+
+/* Workspace bytes of sn_knn_points over `total` rows in B tiles on a grid of cells_per_tile cells per tile (about 36 B per
+ * row, 8 B per cell, 40 B per chunk); 0 for what the entry refuses (total < 1 or >= 2^31, B < 1, cells_per_tile < 1, B *
+ * cells_per_tile > 2^22).  sn_knn_tile_stats uses the leading bytes of the same workspace, whatever the grid. */
+size_t sn_knn_ws_bytes(int64_t total, int B, int64_t cells_per_tile);
+
+/* The search.  k in 1 .. SN_KNN_MAX_K (kept in registers by kernels built for 1, 4, 8 and 16 columns; a k in between runs
+ * the next one and stores its first k columns).  SN_KNN_LAUNCHES launches on `stream`, a launch that zeroes the cell
+ * populations in front of them (a kernel, not a memset node); integer atomics only, no allocation, no synchronisation:
+ * capturable.  radius, dims and mult travel as kernel arguments; pts, offsets and
+ * lo are device memory: a replay follows their current contents.
+ * SN_ERR_INVALID_ARG: a null pts / offsets / lo / ws / d2 / found, total <= 0, B <= 0, k < 1, a radius that is not finite
+ * or <= 0, a dim or mult < 1, unknown flags, pts / offsets / lo / d2 / mean_dist / index not 8-byte, found not 4-byte, ws
+ * not 16-byte aligned, ws_bytes < sn_knn_ws_bytes(total, B, dim_x * dim_y * dim_z);  SN_ERR_UNSUPPORTED: k > SN_KNN_MAX_K,
+ * total >= 2^31, more than 2^22 cells, a radius outside 1e-150 .. 1e150, mult * radius not finite.  All checked before any
+ * launch. */
+int sn_knn_points(const double* pts, const int64_t* offsets, int64_t total, int B, double radius, int k, int flags,
+                  const double* lo, int dim_x, int dim_y, int dim_z, int64_t mult, void* ws, size_t ws_bytes, double* d2,
+                  int32_t* found, double* mean_dist, int64_t* index, sn_stream_t stream);
+
+/* DIAGNOSTIC entry, no part of the stable interface: the launches first..last (1-based, of SN_KNN_LAUNCHES) of the same
+ * call and nothing else; tools/knn_bench.py times the prefixes 1..k through it and takes differences.  Launches left out
+ * must have run before on the same workspace. */
+int sn_knn_points_launches(const double* pts, const int64_t* offsets, int64_t total, int B, double radius, int k, int flags,
+                           const double* lo, int dim_x, int dim_y, int dim_z, int64_t mult, void* ws, size_t ws_bytes,
+                           double* d2, int32_t* found, double* mean_dist, int64_t* index, int first, int last,
+                           sn_stream_t stream);
+
+/* The statistics above from mean_dist and found as sn_knn_points left them (k: the same k).  Two launches (partials,
+ * combine), every slot written by one workgroup; capturable.  ws: the workspace of sn_knn_points, or any 16-byte aligned
+ * scratch of sn_knn_ws_bytes(total, B, 1) bytes.
+ * SN_ERR_INVALID_ARG: a null pointer, total <= 0, B <= 0, k < 1, a misaligned pointer, a short workspace;
+ * SN_ERR_UNSUPPORTED: k > SN_KNN_MAX_K, total >= 2^31, B > 65535. */
+int sn_knn_tile_stats(const double* mean_dist, const int32_t* found, const int64_t* offsets, int64_t total, int B, int k,
+                      void* ws, size_t ws_bytes, double* stats, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

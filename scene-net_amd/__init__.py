@@ -37,6 +37,8 @@ from .thin import (ThinnedPoints, ThinPoints, downsampling, downsampling_relativ
                    philox_uniforms, thin_points, uniform_thresholds)
 from .voxel_classes import (ClassColors, VoxelClasses, class_colors, classes_on_voxel, color_pointcloud,
                             random_class_colors, voxel_classes)
+from .neighbours import (PointNeighbours, avg_dist_points, k_distance_curve, knn_distances, point_spacing,
+                         remove_outliers)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalLoss, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss,
                          GENEO_Loss, GENEO_Tversky_Loss, IoULoss, QuantileGENEOLoss, QuantileLoss, TverskyLoss, WeightedMSE)
 
@@ -55,7 +57,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "ThinnedPoints", "ThinPoints", "thin_points", "downsampling", "downsampling_relative_height", "height_thresholds",
            "uniform_thresholds", "philox_uniforms",
            "VoxelClasses", "ClassColors", "voxel_classes", "classes_on_voxel", "class_colors", "color_pointcloud",
-           "random_class_colors",
+           "random_class_colors", "PointNeighbours", "knn_distances", "point_spacing", "k_distance_curve", "remove_outliers",
+           "avg_dist_points",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE", "QuantileLoss", "QuantileGENEOLoss", "FocalLoss", "IoULoss"]

@@ -151,6 +151,13 @@ SYMBOLS = {
                               _P]),
     "sn_quantile_forward": (c_int, [_P, _I, _P, _I, _I, _I, ctypes.c_int64, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "sn_quantile_backward": (c_int, [_P, _I, _P, _I, _I, _I, ctypes.c_int64, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "sn_knn_chunk_points": (c_int, []),
+    "sn_knn_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I, ctypes.c_int64]),
+    "sn_knn_points": (c_int, [_P, _P, ctypes.c_int64, _I, ctypes.c_double, _I, _I, _P, _I, _I, _I, ctypes.c_int64, _P,
+                              ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "sn_knn_points_launches": (c_int, [_P, _P, ctypes.c_int64, _I, ctypes.c_double, _I, _I, _P, _I, _I, _I, ctypes.c_int64, _P,
+                                       ctypes.c_size_t, _P, _P, _P, _P, _I, _I, _P]),
+    "sn_knn_tile_stats": (c_int, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, ctypes.c_size_t, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -171,6 +178,7 @@ SN_CLOUD_DENSITY, SN_CLOUD_RANGES, SN_CLOUD_MAX_R = 0, 1, 32
 SN_THIN_GROUP_NONE, SN_THIN_GROUP_Z, SN_THIN_GROUP_VOXEL = 0, 1, 2
 SN_CLASS_WORDS, SN_VOXEL_CLASSES_NO_SKIP = 2048, 1
 SN_MERGE_MAX, SN_MERGE_MEAN, SN_MERGE_INTERIOR = 0, 1, 2
+SN_KNN_MAX_K, SN_KNN_NSTAT, SN_KNN_LAUNCHES, SN_KNN_EXCLUDE_ZERO = 16, 5, 4, 1
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -2095,3 +2103,58 @@ def scan_merge(grid: torch.Tensor, desc: torch.Tensor, pts: torch.Tensor, region
                               _ptr(kinds, torch.int32, "kinds"), _ptr(tile_of, torch.int32, "tile_of"), K, int(rule),
                               float(fill), _ptr(out, None, "out"), _ptr(cover, torch.int32, "cover"), _stream())
     _check(rc, "sn_scan_merge")
+
+
+# --------------------------------------------------------------------------- #
+def knn_chunk_points() -> int:
+    """sn_knn_chunk_points: rows per workgroup of the neighbour kernels and per partial of their statistics (host only)."""
+    return int(load().sn_knn_chunk_points())
+
+
+def knn_ws_bytes(total: int, B: int, cells_per_tile: int) -> int:
+    """sn_knn_ws_bytes: scratch bytes of knn_points / knn_tile_stats over `total` rows in B tiles (host only)."""
+    need = int(load().sn_knn_ws_bytes(int(total), int(B), int(cells_per_tile)))
+    if need == 0:
+        raise HipLibraryError(f"sn_knn_points serves no batch of {total} rows in {B} tiles on {cells_per_tile} cells per tile "
+                              "(1 <= total < 2^31, B * cells <= 2^22)")
+    return need
+
+
+@_on_tensor_device
+def knn_points(pts: torch.Tensor, offsets: torch.Tensor, radius: float, k: int, lo: torch.Tensor, dims: Sequence[int], mult: int,
+               ws: torch.Tensor, d2: torch.Tensor, found: torch.Tensor, mean_dist: Optional[torch.Tensor] = None,
+               index: Optional[torch.Tensor] = None, exclude_zero: bool = False,
+               launches: Optional[Tuple[int, int]] = None) -> None:
+    """sn_knn_points: pts [total,3] f64, offsets [B+1] i64, lo [B,3] f64 -> d2 [total,k] f64, found [total] i32, mean_dist
+    [total] f64 | None, index [total,k] i64 | None, all caller-owned like the scratch `ws` (knn_ws_bytes).  dims, mult: the
+    grid (dbscan_cell_grid).  launches = (first, last): only those of the SN_KNN_LAUNCHES launches
+    (sn_knn_points_launches: timing).  No allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [n, 3] (got {tuple(pts.shape)})")
+    total, B, k = int(pts.shape[0]), int(offsets.numel()) - 1, int(k)
+    if lo.numel() != 3 * B or d2.numel() != total * k or found.numel() != total or \
+            (mean_dist is not None and mean_dist.numel() != total) or (index is not None and index.numel() != total * k):
+        raise HipLibraryError("lo / d2 / found / mean_dist / index do not have the sizes of this call")
+    head = (_ptr(pts, torch.float64, "pts"), _ptr(offsets, torch.int64, "offsets"), total, B, float(radius), k,
+            SN_KNN_EXCLUDE_ZERO if exclude_zero else 0, _ptr(lo, torch.float64, "lo"), int(dims[0]), int(dims[1]), int(dims[2]),
+            int(mult), _ptr(ws, None, "ws"), ws.numel() * ws.element_size(), _ptr(d2, torch.float64, "d2"),
+            _ptr(found, torch.int32, "found"), _ptr(mean_dist, torch.float64, "mean_dist"), _ptr(index, torch.int64, "index"))
+    if launches is None:
+        rc = load().sn_knn_points(*head, _stream())
+    else:
+        rc = load().sn_knn_points_launches(*head, int(launches[0]), int(launches[1]), _stream())
+    _check(rc, "sn_knn_points")
+
+
+@_on_tensor_device
+def knn_tile_stats(mean_dist: torch.Tensor, found: torch.Tensor, offsets: torch.Tensor, k: int, ws: torch.Tensor,
+                   stats: torch.Tensor) -> None:
+    """sn_knn_tile_stats: mean_dist [total] f64 and found [total] i32 of knn_points -> stats [B, SN_KNN_NSTAT] f64 (n_valid,
+    n_full, sum, sum_sq, max per tile) in a fixed order.  No allocation, no synchronisation."""
+    total, B = int(found.numel()), int(offsets.numel()) - 1
+    if mean_dist.numel() != total or stats.numel() != B * SN_KNN_NSTAT:
+        raise HipLibraryError("mean_dist / stats do not have the sizes of this call")
+    rc = load().sn_knn_tile_stats(_ptr(mean_dist, torch.float64, "mean_dist"), _ptr(found, torch.int32, "found"),
+                                  _ptr(offsets, torch.int64, "offsets"), total, B, int(k), _ptr(ws, None, "ws"),
+                                  ws.numel() * ws.element_size(), _ptr(stats, torch.float64, "stats"), _stream())
+    _check(rc, "sn_knn_tile_stats")
