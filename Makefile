@@ -41,7 +41,7 @@ OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so
 
-$(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(SRC)/conv_prep.h $(SRC)/binning.h $(SRC)/scan.h $(SRC)/regions.h $(SRC)/loss_common.h $(SRC)/cell_grid.h
+$(OBJDIR)/%.o: $(SRC)/%.hip include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(wildcard $(SRC)/*.h)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(CXXFLAGS) $(FLAGS_$*) -c $< -o $@
 

@@ -11,21 +11,14 @@
 // neighbours; cluster: a connected component of the cores, ids ascending with the smallest core position; border: not core
 // with a core neighbour, takes the smallest id among them; everything else -1.
 //
-// The cell grid is an accelerator only: cubic cells of side k * eps * (1 + 2^-20) from bounds' minimum, points binned by
-// axis_cell (monotone, clamped), so that neighbours never sit two cells apart (proof at axis_cell, cell_grid.h) and the 27 cells around
-// a point's own hold every neighbour.  Points are counting-sorted into cell order as rows (x, y, z, position, cell); with z
-// the fastest cell axis the three cells of one (x, y) column are ONE contiguous run of rows: 9 runs per home point.  The
-// order of rows inside a cell depends on scheduling (an integer cursor); every result is a count, a minimum or a set
-// union over the run, so none does.
+// The selected positions are counting-sorted into the cell grid of cell_grid.h (cells from bounds' minimum), an
+// accelerator only: the 9 runs of rows around a point's own cell hold every neighbour.
 //   select:  count (members and the finite box per 1024 points) -> prefix (one workgroup) -> scatter (ballot + mbcnt: scan order)
 //   1 cells    cell of every selected position, population per cell (integer atomics); status
-//   2 prefix   exclusive prefix of the populations (one workgroup), cursors
-//   3 scatter  rows into cell order
+//   2 prefix   cell_starts
+//   3 scatter  scatter_row
 //   4 core     neighbours counted over the 9 runs with an exit at min_points; parent[p] = p for a core, -1 otherwise
-//   5 union    lock-free union-find over POSITIONS (K8's discipline: relaxed agent-scope accesses, a hook is a compare-
-//              and-swap of a root that expects itself, the larger root goes under the smaller: a parent is always a
-//              smaller position, every loop is bounded by the data, no workgroup waits for another); each pair is
-//              taken once, by its larger position
+//   5 union    lock-free union-find over POSITIONS (union_find.h); each pair is taken once, by its larger position
 //   6 flatten  parent[p] = root(p); a root's rank inside its 256 positions and the roots per 256 positions
 //   7 rank     exclusive prefix of those counts (one workgroup): id = roots in front = rank by smallest core position;
 //              n_clusters; stats zeroed
@@ -40,6 +33,7 @@
 #include "common.h"
 #include "cell_grid.h"
 #include "scan.h"
+#include "union_find.h"
 #include <cmath>
 
 namespace {
@@ -48,19 +42,9 @@ constexpr int kThreads = 256;
 constexpr int kSelGroups = 4;
 constexpr int kSelChunk = kThreads * kSelGroups;   // scan points per workgroup of the select kernels
 constexpr int kRankChunk = kThreads;               // positions per workgroup of launches 1, 3..6, 8
-constexpr int kScanThreads = 1024;                 // the one-workgroup prefix kernels (their own tile, not scan.h's)
-constexpr int kScanItems = 4;
 constexpr int kMaxKeep = 64;
 constexpr int64_t kMaxN = (int64_t)1 << 33;
-constexpr int64_t kMaxCells = (int64_t)1 << 22;
 constexpr int kMaxClusters = 1 << 20;
-constexpr double kSideMargin = 1.0 + 0x1p-20;
-constexpr double kEpsMin = 1e-150, kEpsMax = 1e150;   // eps * eps is a normal number
-
-struct __attribute__((aligned(16))) Row {
-    double x, y, z;
-    int pos, cell;
-};
 
 // the neighbour test in exactly the documented form
 __device__ __forceinline__ bool is_near(const Row& q, double x, double y, double z, double eps2) {
@@ -94,21 +78,6 @@ __device__ __forceinline__ void load_position(const double* __restrict__ pts, co
     x = pts[s * 3];
     y = pts[s * 3 + 1];
     z = pts[s * 3 + 2];
-}
-
-// f(row) for every row of the 27 cells around `cell`, until it returns false: 9 contiguous runs
-template <typename F>
-__device__ __forceinline__ void for_candidates(const CellGrid& g, const int32_t* __restrict__ start,
-                                               const Row* __restrict__ rows, int m, int cell, F&& f) {
-    const int cz = cell % g.dim[2], t = cell / g.dim[2], cy = t % g.dim[1], cx = t / g.dim[1];
-    const int zlo = max(cz - 1, 0), zhi = min(cz + 1, g.dim[2] - 1);
-    for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.dim[0] - 1); ++ax)
-        for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.dim[1] - 1); ++ay) {
-            const int base = (ax * g.dim[1] + ay) * g.dim[2];
-            const int a = max(start[base + zlo], 0), b = min(start[base + zhi + 1], m);
-            for (int j = a; j < b; ++j)
-                if (!f(rows[j])) return;
-        }
 }
 
 // ------------------------------------------------------------------------------------------------------------- select
@@ -278,29 +247,14 @@ __global__ __launch_bounds__(kThreads) void dbscan_cells_kernel(const double* __
     atomicAdd(pop + c, 1);
 }
 
-// ---- 2: one workgroup.  start[c] = rows in the cells before c, start[cells] = m; pop[c] becomes cell c's cursor
+// ---- 2: one workgroup: the cells' starts and cursors
 __global__ __launch_bounds__(kScanThreads) void dbscan_prefix_kernel(int32_t* __restrict__ pop, int cells,
                                                                      int32_t* __restrict__ start) {
     __shared__ int64_t s_wave[kScanThreads / 64];
-    int64_t carry = 0;
-    for (int t0 = 0; t0 < cells; t0 += kScanThreads * kScanItems) {
-        const int c0 = t0 + threadIdx.x * kScanItems;
-        int64_t v[kScanItems];
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) v[q] = c0 + q < cells ? pop[c0 + q] : 0;
-        const int64_t total = sn::block_exclusive<kScanThreads, kScanItems>(v, s_wave);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q)
-            if (c0 + q < cells) {
-                start[c0 + q] = (int32_t)(carry + v[q]);
-                pop[c0 + q] = (int32_t)(carry + v[q]);
-            }
-        carry += total;
-    }
-    if (threadIdx.x == 0) start[cells] = (int32_t)carry;
+    cell_starts(pop, cells, start, s_wave);
 }
 
-// ---- 3: rows into cell order.  The slot inside a cell is whatever the cursor hands out.
+// ---- 3: rows into cell order
 __global__ __launch_bounds__(kThreads) void dbscan_scatter_kernel(const double* __restrict__ pts,
                                                                   const int64_t* __restrict__ sel, int64_t n,
                                                                   const int64_t* __restrict__ n_sel, int64_t fallback,
@@ -314,8 +268,7 @@ __global__ __launch_bounds__(kThreads) void dbscan_scatter_kernel(const double* 
     load_position(pts, sel, n, i, r.x, r.y, r.z);
     r.pos = i;
     r.cell = cell_of[i];
-    const int slot = atomicAdd(cursor + r.cell, 1);
-    if ((unsigned)slot < (unsigned)m) rows[slot] = r;   // (always, behind launches 1 and 2 of the same call)
+    scatter_row(r, m, cursor, rows);
 }
 
 // ---- 4: core points.  parent[p] = p for a core, -1 for everything else
@@ -335,49 +288,7 @@ __global__ __launch_bounds__(kThreads) void dbscan_core_kernel(const int64_t* __
     if ((unsigned)me.pos < (unsigned)m) parent[me.pos] = cnt >= min_points ? me.pos : -1;
 }
 
-// ---- union-find over parent[] (positions), as towers.hip's: a stale value is an earlier parent, still an ancestor; only a
-// compare-and-swap that finds a root unchanged ever hooks it
-__device__ __forceinline__ int32_t uf_load(const int32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void uf_store(int32_t* p, int32_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// root of v, halving the path on the way (v strictly decreases: bounded)
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t v) {
-    for (;;) {
-        const int32_t a = uf_load(parent + v);
-        if (a == v) return v;
-        const int32_t g = uf_load(parent + a);
-        if (g == a) return a;
-        uf_store(parent + v, g);
-        v = g;
-    }
-}
-__device__ __forceinline__ int32_t uf_find_readonly(const int32_t* parent, int32_t v) {
-    for (;;) {
-        const int32_t a = uf_load(parent + v);
-        if (a == v) return v;
-        v = a;
-    }
-}
-// unites the sets of a and b, returns the root seen last.  A failed compare-and-swap means a is no root any more: the
-// value it returns is a's parent, a smaller position.
-__device__ __forceinline__ int32_t uf_unite(int32_t* parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return a;
-        if (a < b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        const int32_t old = atomicCAS(parent + a, a, b);   // the larger root goes under the smaller
-        if (old == a) return b;
-        a = old;
-    }
-}
+// ---- union-find over parent[] (union_find.h): the indices are positions
 
 // ---- 5: every core unites with its core neighbours of smaller position (the pair's other half is that one's business)
 __global__ __launch_bounds__(kThreads) void dbscan_union_kernel(const int64_t* __restrict__ n_sel, int64_t fallback,
@@ -495,9 +406,9 @@ __global__ __launch_bounds__(kThreads) void dbscan_finish_kernel(const int64_t* 
 // ------------------------------------------------------------------------------------------------------------------ host
 int64_t select_chunks(int64_t n) { return (n + kSelChunk - 1) / kSelChunk; }
 
-// dims of the grid with cells of side fl(fl(k * eps) * (1 + 2^-20)); false if it has more than max_cells cells
+// dims of the grid with cells of side cell_side(k, eps); false if it has more than max_cells cells
 bool dims_at(const double* extent, double eps, double k, int64_t max_cells, int* dim, double* side_out) {
-    const double side = k * eps * kSideMargin;
+    const double side = cell_side(k, eps);
     int64_t cells = 1;
     for (int a = 0; a < 3; ++a) {
         const double d = std::floor(extent[a] / side) + 1.0;

@@ -10,12 +10,12 @@
 // (d2, row index) ascending; mean_dist = the ascending sum of their square roots over their number.  Every result is a
 // function of the candidate SET: the list is ordered by a total order on (d2, row), found is a count.
 //
-// The grid is K10's (cell_grid.h): cubic cells of side mult * radius * (1 + 2^-20) from each tile's own lo, the cell key
-// tile * cells_per_tile + local cell, so tiles never meet.  Rows are counting-sorted into cell order as (x, y, z, row, key).
+// The rows are counting-sorted into the cell grid of cell_grid.h, with eps = radius and k = mult, from each tile's own lo:
+// the cell key is tile * cells_per_tile + local cell, so tiles never meet; a Row is (x, y, z, row index, key).
 //   1 cells    tile (binary search in offsets) and cell of every row, populations (integer atomics, zeroed by a small
 //              launch in front); rows that no tile owns get their empty result here
-//   2 prefix   exclusive prefix of the populations (one workgroup), cursors
-//   3 scatter  rows into cell order
+//   2 prefix   cell_starts
+//   3 scatter  scatter_row
 //   4 search   one thread per row IN CELL ORDER: the 9 runs of the 27 cells, the k best in registers (compile-time K in
 //              {1, 4, 8, 16}, insertion by an unrolled compare-and-shift: no runtime-indexed private array), results stored
 //              at the row's own index
@@ -32,18 +32,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = kThreads;        // rows per workgroup of launches 1, 3, 4 and per partial of the statistics
-constexpr int kScanThreads = 1024;      // the one-workgroup prefix kernel (K10's tile)
-constexpr int kScanItems = 4;
 constexpr int kStatParts = 128;         // workgroups per tile of the partials kernel
 constexpr int kMaxK = SN_KNN_MAX_K;
-constexpr int64_t kMaxCells = (int64_t)1 << 22;
-constexpr double kSideMargin = 1.0 + 0x1p-20;
-constexpr double kEpsMin = 1e-150, kEpsMax = 1e150;   // radius * radius is a normal number
-
-struct __attribute__((aligned(16))) Row {
-    double x, y, z;
-    int pos, cell;
-};
 
 __device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
@@ -99,29 +89,14 @@ __global__ __launch_bounds__(kThreads) void knn_cells_kernel(const double* __res
     atomicAdd(pop + c, 1);
 }
 
-// ---- 2: one workgroup.  start[c] = rows in the cells before c, start[cells] = m; pop[c] becomes cell c's cursor
+// ---- 2: one workgroup: the cells' starts and cursors
 __global__ __launch_bounds__(kScanThreads) void knn_prefix_kernel(int32_t* __restrict__ pop, int cells,
                                                                   int32_t* __restrict__ start) {
     __shared__ int64_t s_wave[kScanThreads / 64];
-    int64_t carry = 0;
-    for (int t0 = 0; t0 < cells; t0 += kScanThreads * kScanItems) {
-        const int c0 = t0 + threadIdx.x * kScanItems;
-        int64_t v[kScanItems];
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q) v[q] = c0 + q < cells ? pop[c0 + q] : 0;
-        const int64_t total = sn::block_exclusive<kScanThreads, kScanItems>(v, s_wave);
-#pragma unroll
-        for (int q = 0; q < kScanItems; ++q)
-            if (c0 + q < cells) {
-                start[c0 + q] = (int32_t)(carry + v[q]);
-                pop[c0 + q] = (int32_t)(carry + v[q]);
-            }
-        carry += total;
-    }
-    if (threadIdx.x == 0) start[cells] = (int32_t)carry;
+    cell_starts(pop, cells, start, s_wave);
 }
 
-// ---- 3: rows into cell order.  The slot inside a cell is whatever the cursor hands out.
+// ---- 3: rows into cell order
 __global__ __launch_bounds__(kThreads) void knn_scatter_kernel(const double* __restrict__ pts,
                                                                const int64_t* __restrict__ offsets, int total, int B,
                                                                const int32_t* __restrict__ cell_of,
@@ -135,8 +110,7 @@ __global__ __launch_bounds__(kThreads) void knn_scatter_kernel(const double* __r
     r.z = pts[(size_t)i * 3 + 2];
     r.pos = i;
     r.cell = cell_of[i];
-    const int slot = atomicAdd(cursor + r.cell, 1);
-    if ((unsigned)slot < (unsigned)m) rows[slot] = r;   // (always, behind launches 1 and 2 of the same call)
+    scatter_row(r, m, cursor, rows);
 }
 
 // ---- 4: the search.  (v, p) sorts in front of (d, i) iff v < d, or v == d and p < i
@@ -184,6 +158,7 @@ __global__ __launch_bounds__(kThreads) void knn_search_kernel(const int64_t* __r
     best.clear();
     int found = 0;
     const int tile = me.cell / g.cells, local = me.cell - tile * g.cells;
+    // the 9 runs of for_candidates (cell_grid.h) on the tile's slice of start, in a loop of the kernel's own
     const int32_t* __restrict__ tstart = start + (size_t)tile * g.cells;
     const int cz = local % g.dim[2], t = local / g.dim[2], cy = t % g.dim[1], cx = t / g.dim[1];
     const int zlo = max(cz - 1, 0), zhi = min(cz + 1, g.dim[2] - 1);
@@ -383,7 +358,7 @@ int run(const double* pts, const int64_t* offsets, int64_t total, int B, double 
         return sn::fail(SN_ERR_UNSUPPORTED, "%s: more than 2^22 cells (B * dims = %d * %d * %d * %d)", who, B, dim_x, dim_y, dim_z);
     if (radius < kEpsMin || radius > kEpsMax)
         return sn::fail(SN_ERR_UNSUPPORTED, "%s: radius beyond what is served (1e-150 .. 1e150)", who);
-    const double side = (double)mult * radius * kSideMargin;
+    const double side = cell_side((double)mult, radius);
     if (!std::isfinite(side)) return sn::fail(SN_ERR_UNSUPPORTED, "%s: mult * radius is not finite", who);
     if ((uintptr_t)pts % 8 || (uintptr_t)offsets % 8 || (uintptr_t)lo % 8 || (uintptr_t)ws % 16 || (uintptr_t)d2 % 8 ||
         (uintptr_t)found % 4 || (uintptr_t)mean_dist % 8 || (uintptr_t)index % 8)

@@ -8,10 +8,8 @@
 // are the set bits.  Six launches, tiles independent throughout:
 //   1 threshold  grid >= tau -> "positive" bitmap (a wave per word, one ballot)
 //   2 core       positive and >= min_points positives inside the stencil -> "core" bitmap; parent[v] = v for cores
-//   3 union      lock-free union-find over the cores: every core unites with the cores of the backward half of its
-//                stencil; the larger root is hooked under the smaller by compare-and-swap, so a component's root is its
-//                smallest index (ECL-CC).  A parent is always a smaller ancestor: every loop is bounded by the data.  No workgroup
-//                waits for another anywhere.
+//   3 union      lock-free union-find over the cores (union_find.h): every core unites with the cores of the backward
+//                half of its stencil; a component's root is its smallest index
 //   4 flatten    parent[v] = root(v) (read-only walks: only v's own thread writes parent[v]) and the "root" bitmap
 //   5 rank       per tile, the exclusive prefix of the root bitmap's population counts: cluster id = number of roots in
 //                front of a root = rank by smallest core voxel; n_towers; the tile's statistics rows initialised
@@ -24,6 +22,7 @@
 // Bound: launches 1 and 6 by HBM (the grid read once, the labels written once); 2, 3 by LDS / L2 reads per positive voxel.
 #include "common.h"
 #include "scan.h"
+#include "union_find.h"
 #include <cmath>
 #include <type_traits>
 
@@ -153,53 +152,7 @@ __global__ __launch_bounds__(kThreads) void towers_core_kernel(const uint64_t* _
     }
 }
 
-// ---- union-find over parent[] (tile-local padded voxel indices).  Relaxed agent-scope accesses: a stale value is an
-// earlier parent, which is still an ancestor; only a compare-and-swap that finds a root unchanged ever hooks it.
-__device__ __forceinline__ int32_t uf_load(const int32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void uf_store(int32_t* p, int32_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of v, halving the path on the way (v strictly decreases: bounded).  A non-root's parent is only ever replaced by
-// another of its ancestors -- always smaller than the node, though a racing halving store may put back a nearer one.
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t v) {
-    for (;;) {
-        const int32_t a = uf_load(parent + v);
-        if (a == v) return v;
-        const int32_t g = uf_load(parent + a);
-        if (g == a) return a;
-        uf_store(parent + v, g);
-        v = g;
-    }
-}
-
-__device__ __forceinline__ int32_t uf_find_readonly(const int32_t* parent, int32_t v) {
-    for (;;) {
-        const int32_t a = uf_load(parent + v);
-        if (a == v) return v;
-        v = a;
-    }
-}
-
-// unites the sets of a and b, returns the root seen last.  A failed compare-and-swap means a is no root any more: the
-// value it returns is a's parent, a smaller index.
-__device__ __forceinline__ int32_t uf_unite(int32_t* parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return a;
-        if (a < b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        const int32_t old = atomicCAS(parent + a, a, b);   // the larger root goes under the smaller
-        if (old == a) return b;
-        a = old;
-    }
-}
+// ---- union-find over parent[] (union_find.h): the indices are tile-local padded voxel indices
 
 // ---- 3: every core unites with the cores of the backward half of its stencil (the forward half is the other voxel's
 // backward half).  In its own row the nearest core in front suffices: the cores between are that one's business.

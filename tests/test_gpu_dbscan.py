@@ -177,7 +177,7 @@ def test_select_prefix_carries_into_the_second_scan_tile(hip_device):
     """The select's prefix kernel is one workgroup of 1024 threads, one chunk of 1024 points each: one chunk more than that
     and a little, so the prefixes of chunk 1024 and n_sel hold a carry."""
     c = _hip.points_select_chunk_points()
-    tile = 1024                                      # kScanThreads of dbscan.hip
+    tile = 1024                                      # kScanThreads of cell_grid.h
     n = (tile + 1) * c + 3
     rng = np.random.default_rng(1025)
     P = dc.ORIGIN + rng.random((n, 3)) * 50.0
