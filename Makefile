@@ -35,8 +35,10 @@ FLAGS_voxel_classes := -ffp-contract=off
 FLAGS_scan_merge := -ffp-contract=off
 # knn.hip: a squared distance is (dx*dx + dy*dy) + dz*dz and a mean a sum of square roots over a count, every fp64 operation rounded once
 FLAGS_knn := -ffp-contract=off
+# shape.hip: K21's candidate test, a fixed-point offset rint(fl(q - p) * inv), and a covariance and a Jacobi solver whose fp64 operations are rounded once each
+FLAGS_shape := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn shape
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

@@ -1567,6 +1567,100 @@ int sn_knn_tile_stats(const double* mean_dist, const int32_t* found, const int64
                       void* ws, size_t ws_bytes, double* stats, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K22 -- the shape of a point's neighbourhood: covariance, eigenvalues, normal, principal axis and eigenfeatures of every
+ * point's neighbours within a radius, on K10's cell grid.
+ * replaces: nothing in the reference (unit_vector / angle_between in utils/pcd_processing.py only orient crops).  This is
+ *           THIS project's definition of what every point-cloud toolbox offers per point; ground is planar, a conductor
+ *           linear and horizontal, a tower linear and upright, vegetation scattered.
+ *
+ * batch:     K21's: pts [total,3] f64 with offsets [B+1] i64 on the DEVICE, offsets[0] = 0 and offsets[B] <= total; tiles
+ *            never see each other; empty tiles are legal.
+ * candidate: K21's test: a row q of the same tile with d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius in fp64, in exactly
+ *            this form, each product and sum rounded once and never contracted, the comparison literal: a row with a NaN
+ *            or infinite coordinate has no neighbours and is nobody's neighbour.
+ * grid:      K21's, an accelerator only: cubic cells of side mult * radius * (1 + 2^-20), derived HERE from radius and the
+ *            integer mult >= 1, laid from tile b's own lo [B,3] f64 (device), dims host integers shared by all tiles, B *
+ *            dim_x * dim_y * dim_z <= 2^22 (sn_dbscan_cell_grid).  The result is exact for ANY finite lo and any dims >= 1.
+ * neighbourhood of row p: p itself and every candidate q != p -- all of them, no cap, duplicates included.
+ * count:     found + 1 for a live row that passes its own test (d2 = 0: every finite coordinate), 0 otherwise.
+ * moments, in fixed point: with inv = 65536.0 / radius (host, one rounding, a kernel argument) every member contributes
+ *            f_a = (int64) rint(fl(q_a - p_a) * inv) for a in {x, y, z}: the difference and the product rounded once each,
+ *            rint rounds half to even.  |fl(q_a - p_a)| <= radius (1 + 2^-51) (a member has fl(d_a*d_a) <= fl(radius*radius),
+ *            both normal), so |f_a| <= 65537 and f_a is an int32.  The nine moments are int64 sums: S1[3] = sum f_a and
+ *            S2[6] = sum f_a * f_b in the order xx, xy, xz, yy, yz, zz.  Integer sums are exact and order-independent: two
+ *            runs, any grid and any permutation of the rows give the same bits.  total <= 2^30 is required: a neighbourhood
+ *            has at most 2^30 members, |f_a * f_b| <= 65537^2 < 2^32 + 2^18, so |S2| < 2^30 * (2^32 + 2^18) < 2^63 and
+ *            |S1| < 2^47: no sum leaves int64.
+ * covariance, fp64, every operation rounded once, never contracted (int64 -> fp64 conversions round to nearest even):
+ *            n = (double)count, m_a = (double)S1_a / n, C_ab = (double)S2_ab / n - m_a * m_b: the population covariance in
+ *            fixed-point units squared (one unit = radius / 65536).  Cancellation: both terms are at most R2 = 65537^2 <
+ *            2^32.001 in magnitude and carry at most two roundings each (conversion and quotient; quotient and product), the
+ *            difference one more, so |C_ab - exact| <= 5 * 2^-53 * R2 < 2^-18.6 units squared whatever the neighbourhood.
+ *            Offsets are measured from p, a member, so they are at most one radius, not a UTM coordinate; a
+ *            neighbourhood that spreads one unit or more along an axis has a variance of at least (1/n)(1 - 1/n) units squared
+ *            there.  In coordinate units the bound is 2^-18.6 * (radius / 65536)^2 = radius^2 * 2^-50.6.
+ * eigen-decomposition: cyclic Jacobi on the symmetric 3x3 A = C with V = I, SN_SHAPE_SWEEPS sweeps, all executed, each the
+ *            pairs (p, q) = (0,1), (0,2), (1,2) in this order.  A rotation whose a_pq is exactly 0 is skipped (the only
+ *            data-dependent step); otherwise, with r the third index, in + - * / and sqrt only:
+ *              theta = (a_qq - a_pp) / (2 * a_pq)
+ *              u     = 1 / (|theta| + sqrt(theta * theta + 1))      theta * theta may be +inf: u = 0 and t = +-0
+ *              t     = theta < 0 ? -u : u
+ *              c     = 1 / sqrt(t * t + 1),  s = t * c,  h = t * a_pq
+ *              a_pp' = a_pp - h,  a_qq' = a_qq + h,  a_pq' = 0
+ *              a_rp' = c * a_rp - s * a_rq,  a_rq' = s * a_rp + c * a_rq
+ *              v_kp' = c * v_kp - s * v_kq,  v_kq' = s * v_kp + c * v_kq     for k = 0, 1, 2
+ *            The eigenvalues are the diagonal, the eigenvector of a_jj column j of V.  They are sorted ascending by the
+ *            compare-and-swap network (0,1), (1,2), (0,1), a swap only where the left value is GREATER (equal values keep
+ *            their index order), the columns carried along.  A vector is then divided by sqrt((x*x + y*y) + z*z) and
+ *            negated as a whole where z < 0, or z == 0 and y < 0, or z == y == 0 and x < 0.
+ * outputs, indexed by the row's own index in the packed array, each nullable except count:
+ *   count   [total] i32
+ *   moments [total,9] i64: S1 then S2 -- the raw result of the walk
+ *   eig     [total,3] f64: l0 <= l1 <= l2 in squared coordinate units, each lambda_fix * unit2 with unit = radius / 65536.0
+ *           (exact) and unit2 = unit * unit (one rounding)
+ *   normal  [total,3] f64: the unit eigenvector of l0 under the sign rule;  axis [total,3] f64: that of l2
+ *   feat    [total,SN_SHAPE_NFEAT] f64 from the stored eig with negative values clamped to 0 (c0, c1, c2), normal and axis:
+ *           linearity (c2 - c1) / c2, planarity (c1 - c0) / c2, scattering c0 / c2, surface variation c0 / ((c0 + c1) + c2),
+ *           verticality 1 - |normal_z|, uprightness |axis_z|
+ *   A row with count < min_points (an argument >= 3: a plane needs three points) or whose largest fixed-point eigenvalue is
+ *   not > 0 (every member coincides with it) has NaN in eig, normal, axis and feat.  A row at or beyond offsets[B] has
+ *   count 0, zero moments and NaN in the rest.
+ * ------------------------------------------------------------------------- */
+#define SN_SHAPE_SWEEPS 4      /* Jacobi sweeps, all executed; chosen on the host: tests/shape_cases.py */
+#define SN_SHAPE_NFEAT 6       /* linearity, planarity, scattering, surface variation, verticality, uprightness */
+#define SN_SHAPE_LAUNCHES 5    /* zero, cells, prefix, scatter, shape */
+
+/* Rows per workgroup of the kernels (256): host only -- lets a test put its sizes on the seams. */
+int sn_shape_chunk_points(void);
+
+/* Workspace bytes of sn_shape_points over `total` rows in B tiles on a grid of cells_per_tile cells per tile (about 36 B
+ * per row, 8 B per cell); 0 for what the entry refuses (total < 1 or > 2^30, B < 1, cells_per_tile < 1, B * cells_per_tile >
+ * 2^22). */
+size_t sn_shape_ws_bytes(int64_t total, int B, int64_t cells_per_tile);
+
+/* SN_SHAPE_LAUNCHES launches on `stream`, all named shape_*; integer atomics only, no allocation, no synchronisation:
+ * capturable.  radius, min_points, dims and mult travel as kernel arguments; pts, offsets and lo are device memory: a replay
+ * follows their current contents.  flags: none are defined, pass 0.
+ * SN_ERR_INVALID_ARG: a null pts / offsets / lo / ws / count, total <= 0, B <= 0, min_points < 3, a radius that is not
+ * finite or <= 0, a dim or mult < 1, flags != 0, pts / offsets / lo / moments / eig / normal / axis / feat not 8-byte, count
+ * not 4-byte, ws not 16-byte aligned, ws_bytes < sn_shape_ws_bytes(total, B, dim_x * dim_y * dim_z);  SN_ERR_UNSUPPORTED:
+ * total > 2^30, more than 2^22 cells, a radius outside 1e-150 .. 1e150, mult * radius not finite.  All checked before any
+ * launch. */
+int sn_shape_points(const double* pts, const int64_t* offsets, int64_t total, int B, double radius, int min_points,
+                    int flags, const double* lo, int dim_x, int dim_y, int dim_z, int64_t mult, void* ws, size_t ws_bytes,
+                    int32_t* count, int64_t* moments, double* eig, double* normal, double* axis, double* feat,
+                    sn_stream_t stream);
+
+/* DIAGNOSTIC entry, no part of the stable interface: the launches first..last (1-based, of SN_SHAPE_LAUNCHES) of the same
+ * call and nothing else; tools/shape_bench.py times the prefixes through it and takes differences.  Launches left out must
+ * have run before on the same workspace. */
+int sn_shape_points_launches(const double* pts, const int64_t* offsets, int64_t total, int B, double radius, int min_points,
+                             int flags, const double* lo, int dim_x, int dim_y, int dim_z, int64_t mult, void* ws,
+                             size_t ws_bytes, int32_t* count, int64_t* moments, double* eig, double* normal, double* axis,
+                             double* feat, int first, int last, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

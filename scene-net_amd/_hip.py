@@ -158,6 +158,12 @@ SYMBOLS = {
     "sn_knn_points_launches": (c_int, [_P, _P, ctypes.c_int64, _I, ctypes.c_double, _I, _I, _P, _I, _I, _I, ctypes.c_int64, _P,
                                        ctypes.c_size_t, _P, _P, _P, _P, _I, _I, _P]),
     "sn_knn_tile_stats": (c_int, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, ctypes.c_size_t, _P, _P]),
+    "sn_shape_chunk_points": (c_int, []),
+    "sn_shape_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64, _I, ctypes.c_int64]),
+    "sn_shape_points": (c_int, [_P, _P, ctypes.c_int64, _I, ctypes.c_double, _I, _I, _P, _I, _I, _I, ctypes.c_int64, _P,
+                                ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "sn_shape_points_launches": (c_int, [_P, _P, ctypes.c_int64, _I, ctypes.c_double, _I, _I, _P, _I, _I, _I, ctypes.c_int64,
+                                         _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -179,6 +185,7 @@ SN_THIN_GROUP_NONE, SN_THIN_GROUP_Z, SN_THIN_GROUP_VOXEL = 0, 1, 2
 SN_CLASS_WORDS, SN_VOXEL_CLASSES_NO_SKIP = 2048, 1
 SN_MERGE_MAX, SN_MERGE_MEAN, SN_MERGE_INTERIOR = 0, 1, 2
 SN_KNN_MAX_K, SN_KNN_NSTAT, SN_KNN_LAUNCHES, SN_KNN_EXCLUDE_ZERO = 16, 5, 4, 1
+SN_SHAPE_SWEEPS, SN_SHAPE_NFEAT, SN_SHAPE_LAUNCHES = 4, 6, 5
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -2158,3 +2165,47 @@ def knn_tile_stats(mean_dist: torch.Tensor, found: torch.Tensor, offsets: torch.
                                   _ptr(offsets, torch.int64, "offsets"), total, B, int(k), _ptr(ws, None, "ws"),
                                   ws.numel() * ws.element_size(), _ptr(stats, torch.float64, "stats"), _stream())
     _check(rc, "sn_knn_tile_stats")
+
+
+# --------------------------------------------------------------------------- #
+def shape_chunk_points() -> int:
+    """sn_shape_chunk_points: rows per workgroup of the shape kernels (host only)."""
+    return int(load().sn_shape_chunk_points())
+
+
+def shape_ws_bytes(total: int, B: int, cells_per_tile: int) -> int:
+    """sn_shape_ws_bytes: scratch bytes of shape_points over `total` rows in B tiles (host only)."""
+    need = int(load().sn_shape_ws_bytes(int(total), int(B), int(cells_per_tile)))
+    if need == 0:
+        raise HipLibraryError(f"sn_shape_points serves no batch of {total} rows in {B} tiles on {cells_per_tile} cells per "
+                              "tile (1 <= total <= 2^30, B * cells <= 2^22)")
+    return need
+
+
+@_on_tensor_device
+def shape_points(pts: torch.Tensor, offsets: torch.Tensor, radius: float, min_points: int, lo: torch.Tensor,
+                 dims: Sequence[int], mult: int, ws: torch.Tensor, count: torch.Tensor,
+                 moments: Optional[torch.Tensor] = None, eig: Optional[torch.Tensor] = None,
+                 normal: Optional[torch.Tensor] = None, axis: Optional[torch.Tensor] = None,
+                 feat: Optional[torch.Tensor] = None, launches: Optional[Tuple[int, int]] = None) -> None:
+    """sn_shape_points: pts [total,3] f64, offsets [B+1] i64, lo [B,3] f64 -> count [total] i32 and, each or None, moments
+    [total,9] i64, eig / normal / axis [total,3] f64, feat [total,SN_SHAPE_NFEAT] f64, all caller-owned like the scratch
+    `ws` (shape_ws_bytes).  dims, mult: the grid (dbscan_cell_grid).  launches = (first, last): only those of the
+    SN_SHAPE_LAUNCHES launches (sn_shape_points_launches: timing).  No allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [n, 3] (got {tuple(pts.shape)})")
+    total, B = int(pts.shape[0]), int(offsets.numel()) - 1
+    sizes = ((count, total), (moments, total * 9), (eig, total * 3), (normal, total * 3), (axis, total * 3),
+             (feat, total * SN_SHAPE_NFEAT))
+    if lo.numel() != 3 * B or any(t is not None and t.numel() != n for t, n in sizes):
+        raise HipLibraryError("lo / count / moments / eig / normal / axis / feat do not have the sizes of this call")
+    head = (_ptr(pts, torch.float64, "pts"), _ptr(offsets, torch.int64, "offsets"), total, B, float(radius), int(min_points), 0,
+            _ptr(lo, torch.float64, "lo"), int(dims[0]), int(dims[1]), int(dims[2]), int(mult), _ptr(ws, None, "ws"),
+            ws.numel() * ws.element_size(), _ptr(count, torch.int32, "count"), _ptr(moments, torch.int64, "moments"),
+            _ptr(eig, torch.float64, "eig"), _ptr(normal, torch.float64, "normal"), _ptr(axis, torch.float64, "axis"),
+            _ptr(feat, torch.float64, "feat"))
+    if launches is None:
+        rc = load().sn_shape_points(*head, _stream())
+    else:
+        rc = load().sn_shape_points_launches(*head, int(launches[0]), int(launches[1]), _stream())
+    _check(rc, "sn_shape_points")
