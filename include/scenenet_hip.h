@@ -436,6 +436,25 @@ int sn_voxel_occupancy_fused(const double* pts, const double* labels, const int6
                              int32_t* flags, int32_t* dropped, int32_t* counts_ws, int32_t* towers_ws,
                              sn_stream_t stream);
 
+/* What sn_voxel_occupancy (fused = 0: a descriptor is given), sn_voxel_occupancy_fused (fused = 1: the tile's own box) or
+ * sn_voxel_occupancy_sized (sized = 1) would launch for an (nx, ny, nz) grid with `planes` bitmaps (2 with gt_occ, else 1)
+ * and B tiles under the options in force now: host arithmetic only, no launch, no device memory, works without a device.
+ * It evaluates the very text the launches and occ_finalize_kernel evaluate, so they cannot disagree.  The alignment arguments (0 / 1)
+ * say whether pts, labels and bits_ws are 16-byte aligned; want_flags whether `flags` is given.  plan8 (8 x int32, host):
+ *   [0] 1: the one-pass kernel (box, descriptor and bitmap in one launch), 0: the two-kernel form
+ *   [1] z-slabs of the LDS bitmap (1, 2, 4, 8 or 16)
+ *   [2] partial bitmaps per tile that the finalize kernel ORs
+ *   [3] the emptiness proof: 0 none (no flags), 1 on the merged words of the expansion loop, 2 a second pass over the rows
+ *   [4] 1: the finalize kernel takes four words per thread, 0: one
+ *   [5] ny / 32: whole words per (z, x) row
+ *   [6] workgroups per tile of the finalize launch
+ *   [7] dynamic LDS of the binning launch, bytes
+ * Returns SN_OK, SN_ERR_INVALID_ARG (null plan8, an extent or B <= 0, planes outside 1..2) or SN_ERR_UNSUPPORTED exactly
+ * where the launch returns it (no z-slab count fits).  No reference counterpart: this is what lets a test reach, and name,
+ * every fork of the bitmap kernels. */
+int sn_voxel_occupancy_plan(int nx, int ny, int nz, int planes, int B, int fused, int sized, int pts_aligned16,
+                            int labels_aligned16, int ws_aligned16, int want_flags, int32_t* plan8);
+
 /* sn_voxel_occupancy_fused with K2 riding in its first launch: the workgroups that build the 9 x 9 x 9 GENEO bank and the
  * int8 contraction's preparation blob (exactly sn_geneo_bank_prep's: the same arguments from `params` to `prep`, the same
  * bits; with `lambdas` the effective coefficients ride too, as in a training forward's opener sn_geneo_bank_lambdas) are extra grid rows of the bounding-box kernel, so the inference step has no launch, no stream fork and no

@@ -62,6 +62,7 @@ SYMBOLS = {
     "sn_voxel_occupancy": (c_int, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "sn_voxel_occupancy_fused": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
                                          _P]),
+    "sn_voxel_occupancy_plan": (c_int, [_I] * 11 + [_P]),
     "sn_voxel_occupancy_fused_bank": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P,
                                               _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "sn_voxel_occupancy_sized": (c_int, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P,
@@ -814,6 +815,33 @@ def occupancy_supported(n_xyz: Sequence[int], planes: int) -> bool:
             return True
         sl *= 2
     return False
+
+
+class OccupancyPlan(NamedTuple):
+    """sn_voxel_occupancy_plan's eight words (include/scenenet_hip.h)."""
+    one_pass: int        # 1: the one-pass kernel, 0: the two-kernel form
+    slabs: int           # z-slabs of the LDS bitmap
+    parts: int           # partial bitmaps per tile
+    proof: int           # 0 none, 1 on the merged words, 2 a second pass over the rows
+    vec4: int            # the finalize kernel takes four words per thread
+    wpr: int             # ny // 32
+    finalize_blocks: int
+    lds_bytes: int       # dynamic LDS of the binning launch
+
+
+def voxel_occupancy_plan(n_xyz: Sequence[int], planes: int = 1, B: int = 1, fused: bool = False, sized: bool = False,
+                         pts_aligned16: bool = True, labels_aligned16: bool = True, ws_aligned16: bool = True,
+                         want_flags: bool = True) -> Optional[OccupancyPlan]:
+    """What the bitmap entries would launch under the options in force (sn_voxel_occupancy_plan: host only, no launch, no
+    device needed); None where they return SN_ERR_UNSUPPORTED (no z-slab count fits: the counting kernels serve the grid)."""
+    nx, ny, nz = (int(v) for v in n_xyz)
+    p = (ctypes.c_int32 * 8)()
+    rc = load().sn_voxel_occupancy_plan(nx, ny, nz, int(planes), int(B), int(fused), int(sized), int(pts_aligned16),
+                                        int(labels_aligned16), int(ws_aligned16), int(want_flags), ctypes.cast(p, c_void_p))
+    if rc == -2:
+        return None
+    _check(rc, "sn_voxel_occupancy_plan")
+    return OccupancyPlan(*(int(v) for v in p))
 
 
 @_on_tensor_device

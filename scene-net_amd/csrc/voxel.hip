@@ -933,6 +933,24 @@ __device__ __forceinline__ void expand_word<float>(uint32_t m, float* __restrict
                            (float)((m >> (4 * k + 2)) & 1u), (float)((m >> (4 * k + 3)) & 1u));
 }
 
+// ---------------------------------------------------------------- the plan of the bitmap path
+// One text for what the launches pick, what occ_finalize_kernel picks and what sn_voxel_occupancy_plan reports.  The two rules
+// the kernel evaluates are macros, not functions: expanded in place they leave its code object what it was (as inlined
+// device functions they changed its register allocation).
+//
+// The emptiness proof rides on the merged words (`fused`) when a (z,x) row is a power-of-two number (<= a wave's 64) of
+// whole words (wpr = ny >> 5) and the tile's words fill whole waves; never in voxel-size mode (`sized`: the grid is padded
+// to the maximum and only the tile's own n_z x n_x rows, n_y bits each, are the reference's grid -- the padding must not
+// count as an empty row: second pass).
+#define SN_OCC_FUSED_PROOF(want_flags, sized, ny, wpr, words) \
+    ((want_flags) && !(sized) && ((ny) & 31) == 0 && (wpr) >= 1 && (wpr) <= 64 && ((wpr) & ((wpr) - 1)) == 0 && ((words) & 63) == 0)
+// Four words per thread (16-byte loads of the partial bitmaps) where the layout allows -- the finalize grid is sized by
+// that alone (SN_OCC_FIN4) --, unless a fused proof over rows of more than 4 words would then meet lanes of a row group
+// that run different trips (words % 256 != 0).
+#define SN_OCC_FIN4(words, ws_aligned16) (((words) & 3) == 0 && (ws_aligned16))
+#define SN_OCC_VEC4(words, ws_aligned16, fused_proof, wpr) \
+    (SN_OCC_FIN4(words, ws_aligned16) && (!(fused_proof) || (wpr) <= 4 || ((words) & 255) == 0))
+
 // grid (C, B): OR the partial bitmaps, expand bits to the u8 / f32 grids (one 32-voxel word per thread
 // iteration, 16-byte stores), and prove "no y column is full" (an empty (z,x) row exists) -- the tile's
 // flag was raised by occ_partial_kernel and is cleared here by whoever finds an empty row.
@@ -961,10 +979,7 @@ __global__ __launch_bounds__(kThreads) void occ_finalize_kernel(const uint32_t* 
     // words % 64 == 0), the emptiness proof rides on the words this loop has merged anyway; otherwise a second pass
     // re-merges the words of each row.
     const int wpr = ny >> 5;   // words per row
-    // (voxel-size mode, dims != null: the grid is padded to the maximum and only the tile's own n_z x n_x rows, n_y bits
-    // each, are the reference's grid -- the padding must not count as an empty row: second pass)
-    const bool fused_proof = flags && !dims && (ny & 31) == 0 && wpr >= 1 && wpr <= 64 && (wpr & (wpr - 1)) == 0 &&
-                             (words & 63) == 0;
+    const bool fused_proof = SN_OCC_FUSED_PROOF(flags, dims, ny, wpr, words);
     const int own_nx = dims ? dims[b * 3 + 0] : nx, own_ny = dims ? dims[b * 3 + 1] : ny,
               own_nz = dims ? dims[b * 3 + 2] : rows / (nx > 0 ? nx : 1);
     bool empty = false;
@@ -972,7 +987,7 @@ __global__ __launch_bounds__(kThreads) void occ_finalize_kernel(const uint32_t* 
     // per plane -- a quarter of the memory instructions of the word-per-thread loop below ([measured] round 4: 7.0 -> see
     // DESIGN K1).  The emptiness proof of a row rides on the merged words: inside the thread for rows of <= 4 words, by
     // shuffles over the row's lanes for longer rows (then every lane of a row group runs the same trips: words % 256 == 0).
-    const bool vec4 = (words & 3) == 0 && ((uintptr_t)bits_ws & 15) == 0 && (!fused_proof || wpr <= 4 || (words & 255) == 0);
+    const bool vec4 = SN_OCC_VEC4(words, ((uintptr_t)bits_ws & 15) == 0, fused_proof, wpr);
     if (vec4) {
         const int words4 = words >> 2;
         for (int q = gtid; q < words4; q += gstride) {
@@ -1409,6 +1424,36 @@ static bool onepass_eligible(int nx, int ny, int nz, int planes) {
     return sn::option(sn::kOptVoxelOnepass) && V % 32 == 0 && (V / 32) * planes <= (size_t)kMaxOccWords;
 }
 
+// z-slabs: the bitmap(s) of one slab must fit the 64 KiB LDS budget and start on a word boundary.  0: no plan.
+static int occ_slabs(int nx, int ny, int nz, int planes) {
+    const size_t V = (size_t)nx * ny * nz;
+    if (V % 32 == 0)
+        for (int sl = 1; sl <= kOccParts; sl *= 2)
+            if (nz % sl == 0 && (V / 32) % sl == 0 && ((size_t)nz / sl) * nx * ny % 32 == 0 &&
+                (V / 32 / sl) * planes <= (size_t)kMaxOccWords)
+                return sl;
+    return 0;
+}
+static int occ_no_plan(int nx, int ny, int nz, int planes) {
+    return sn::fail(SN_ERR_UNSUPPORTED,
+                    "sn_voxel_occupancy: %zu voxels x %d planes do not fit the LDS bitmap in <= %d z-slabs "
+                    "(use sn_voxel_scatter + sn_voxel_finalize)", (size_t)nx * ny * nz, planes, kOccParts);
+}
+// partial bitmaps per tile (eligibility of the one-pass form implies slabs == 1)
+static int occ_parts(bool onepass, int slabs) { return onepass ? kOneParts : kOccParts / slabs; }
+// dynamic LDS of the binning launch: the edge table (16-byte padded), then one slab's bitmap(s)
+static size_t occ_binning_lds(int nx, int ny, int nz, int words, int planes, int slabs) {
+    const int ne = nx + ny + nz + 3;
+    return (size_t)((ne + 1) & ~1) * sizeof(double) + (size_t)(words / slabs) * planes * sizeof(uint32_t);
+}
+// workgroups per tile of occ_finalize_kernel (four words per thread where it can: see its vec4 path; any grid is correct,
+// the loops stride)
+static int occ_finalize_blocks(int words, bool ws_aligned16, int B) {
+    int C = ((SN_OCC_FIN4(words, ws_aligned16) ? words / 4 : words) + kThreads - 1) / kThreads;
+    if (C > blocks_per_tile(B, 2048)) C = blocks_per_tile(B, 2048);
+    return C;
+}
+
 // sn_voxel_occupancy (descriptor given) and sn_voxel_occupancy_fused (box_parts given: the binning kernel derives the
 // descriptor itself and writes it to `desc`)
 static int occupancy_impl(const double* pts, const double* labels, const int64_t* offsets, int B, double* desc, int nx,
@@ -1431,20 +1476,9 @@ static int occupancy_impl(const double* pts, const double* labels, const int64_t
         return sn::fail(SN_ERR_UNSUPPORTED, "sn_voxel_occupancy: n_keep=%d outside [0,%d] or null list", n_keep,
                         kMaxKeep);
     const size_t V = (size_t)nx * ny * nz;
-    // z-slabs: the bitmap(s) of one slab must fit the 64 KiB LDS budget and start on a word boundary
-    int slabs = 0;
-    if (V % 32 == 0)
-        for (int sl = 1; sl <= kOccParts; sl *= 2)
-            if (nz % sl == 0 && (V / 32) % sl == 0 && ((size_t)nz / sl) * nx * ny % 32 == 0 &&
-                (V / 32 / sl) * planes <= (size_t)kMaxOccWords) {
-                slabs = sl;
-                break;
-            }
-    if (!slabs)
-        return sn::fail(SN_ERR_UNSUPPORTED,
-                        "sn_voxel_occupancy: %zu voxels x %d planes do not fit the LDS bitmap in <= %d z-slabs "
-                        "(use sn_voxel_scatter + sn_voxel_finalize)", V, planes, kOccParts);
-    const int parts = onepass ? kOneParts : kOccParts / slabs;   // (eligibility of the one-pass form implies slabs == 1)
+    const int slabs = occ_slabs(nx, ny, nz, planes);
+    if (!slabs) return occ_no_plan(nx, ny, nz, planes);
+    const int parts = occ_parts(onepass, slabs);
     if (gt_occ && flags && counts_ws && !towers_ws)
         return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy: the counting fallback needs towers_ws for gt_occ");
     const int words = (int)(V / 32);
@@ -1452,8 +1486,7 @@ static int occupancy_impl(const double* pts, const double* labels, const int64_t
     hipStream_t s = sn::as_stream(stream);
     // per-part dropped counts live behind the partial bitmaps in bits_ws (SN_OCC_WS_WORDS accounts for them)
     int32_t* dropped_parts = reinterpret_cast<int32_t*>(bits_ws + (size_t)B * kOccParts * planes * words);
-    const size_t lds1 =
-        (size_t)((ne + 1) & ~1) * sizeof(double) + (size_t)(words / slabs) * planes * sizeof(uint32_t);
+    const size_t lds1 = occ_binning_lds(nx, ny, nz, words, planes, slabs);
     const bool al = aligned16(pts) && (!labels || aligned16(labels));
     unsigned long long* exchange = nullptr;
     if (onepass) {
@@ -1481,10 +1514,7 @@ static int occupancy_impl(const double* pts, const double* labels, const int64_t
                            regular, box_parts ? desc : nullptr, bbox_out);
     }
     const int rows = nz * nx;
-    // (four words per thread where the finalize kernel can: see its vec4 path; any grid is correct, the loops stride)
-    const bool fin4 = (words & 3) == 0 && ((uintptr_t)bits_ws & 15) == 0;
-    int C = ((fin4 ? words / 4 : words) + kThreads - 1) / kThreads;
-    if (C > blocks_per_tile(B, 2048)) C = blocks_per_tile(B, 2048);
+    const int C = occ_finalize_blocks(words, aligned16(bits_ws), B);
     if (out_dtype == SN_U8)
         hipLaunchKernelGGL(occ_finalize_kernel<uint8_t>, dim3(C, B), dim3(kThreads), 0, s, bits_ws, words, planes,
                            parts, rows, ny, V, (uint8_t*)occ, (uint8_t*)gt_occ, flags, dropped_parts, dropped, dims, nx,
@@ -1539,6 +1569,29 @@ extern "C" int sn_voxel_occupancy_fused(const double* pts, const double* labels,
     return occupancy_impl(pts, labels, offsets, B, desc, nx, ny, nz, keep_labels_host, n_keep, bits_ws, occ, gt_occ,
                           out_dtype, flags, dropped, counts_ws, towers_ws, partial_ws, SN_BBOX_PARTS, regular ? 1 : 0,
                           bbox, stream, nullptr, nullptr, one);
+}
+
+extern "C" int sn_voxel_occupancy_plan(int nx, int ny, int nz, int planes, int B, int fused, int sized, int pts_aligned16,
+                                       int labels_aligned16, int ws_aligned16, int want_flags, int32_t* plan8) {
+    if (!plan8) return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy_plan: null plan8");
+    if (B <= 0 || nx <= 0 || ny <= 0 || nz <= 0)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy_plan: non-positive extent (B=%d n=%d,%d,%d)", B, nx, ny, nz);
+    if (planes < 1 || planes > 2) return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy_plan: planes=%d outside 1..2", planes);
+    (void)pts_aligned16; (void)labels_aligned16;   // they pick the binning kernel's 16-byte-load form: no plan word of today's
+    const int slabs = occ_slabs(nx, ny, nz, planes);
+    if (!slabs) return occ_no_plan(nx, ny, nz, planes);
+    const bool one = fused && !sized && onepass_eligible(nx, ny, nz, planes);
+    const int words = (int)((size_t)nx * ny * nz / 32), wpr = ny >> 5;
+    const bool fp = SN_OCC_FUSED_PROOF(want_flags != 0, sized != 0, ny, wpr, words);
+    plan8[0] = one ? 1 : 0;
+    plan8[1] = slabs;
+    plan8[2] = occ_parts(one, slabs);
+    plan8[3] = !want_flags ? 0 : fp ? 1 : 2;
+    plan8[4] = SN_OCC_VEC4(words, ws_aligned16 != 0, fp, wpr) ? 1 : 0;
+    plan8[5] = wpr;
+    plan8[6] = occ_finalize_blocks(words, ws_aligned16 != 0, B);
+    plan8[7] = (int32_t)occ_binning_lds(nx, ny, nz, words, planes, slabs);
+    return SN_OK;
 }
 
 // the bounding-box launch of the fused entry points, with K2's workgroups as riders when a bank is handed in

@@ -67,6 +67,18 @@ def test_argument_checks_need_no_gpu():
     assert lib.sn_conv_corr_plan(0, 4, 1, 8, 8, 16, 3, 3, 17, p) == -2   # bf16 gradients, ky > 16
     assert b"bf16" in lib.sn_last_error()
     assert lib.sn_conv_corr_plan(3, 0, 1, 8, 8, 16, 3, 3, 3, p) == 0
+    # the bitmap path's plan query: host arithmetic, refused like the launch it describes
+    assert lib.sn_voxel_occupancy_plan(64, 64, 64, 1, 1, 0, 0, 1, 1, 1, 1, None) == -1
+    assert b"null" in lib.sn_last_error()
+    for bad in ((0, 64, 64, 1, 1), (64, -1, 64, 1, 1), (64, 64, 0, 1, 1), (64, 64, 64, 1, 0)):
+        assert lib.sn_voxel_occupancy_plan(*bad, 0, 0, 1, 1, 1, 1, p) == -1
+        assert b"non-positive" in lib.sn_last_error()
+    for planes in (0, 3):
+        assert lib.sn_voxel_occupancy_plan(64, 64, 64, planes, 1, 0, 0, 1, 1, 1, 1, p) == -1
+        assert b"planes" in lib.sn_last_error()
+    assert lib.sn_voxel_occupancy_plan(512, 512, 512, 1, 1, 0, 0, 1, 1, 1, 1, p) == -2
+    assert b"LDS bitmap" in lib.sn_last_error()
+    assert lib.sn_voxel_occupancy_plan(64, 64, 64, 2, 1, 1, 0, 1, 1, 1, 1, p) == 0
     assert lib.sn_grid_to_points(None, 0, 4, 4, 4, None, None, p, None) == -1
     assert lib.sn_grid_to_points(p, 0, 4, 0, 4, None, None, p, None) == -1   # empty grid
     assert b"empty" in lib.sn_last_error()
