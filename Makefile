@@ -37,8 +37,10 @@ FLAGS_scan_merge := -ffp-contract=off
 FLAGS_knn := -ffp-contract=off
 # shape.hip: K21's candidate test, a fixed-point offset rint(fl(q - p) * inv), and a covariance and a Jacobi solver whose fp64 operations are rounded once each
 FLAGS_shape := -ffp-contract=off
+# render.hip: a projected coordinate is ((a0*x + a1*y) + a2*z) + a3 with every product and sum rounded once, as numpy rounds them
+FLAGS_render := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn shape
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn shape render
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

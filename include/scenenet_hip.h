@@ -1680,6 +1680,91 @@ int sn_shape_points_launches(const double* pts, const int64_t* offsets, int64_t 
                              double* feat, int first, int last, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K23 -- point clouds to images: a point rasteriser with a z-buffer.
+ * replaces: nothing the reference computes.  Its visualize_ply, plot_voxelgrid(plot=True), visualize_pred_vs_gt,
+ *           plot_centroids and visualize_batch end in a viewer window or a matplotlib 3-D scatter on the host.  This is THIS
+ *           project's definition of an image of a point cloud: K16's, K18's and K22's coloured rows (xyz + 16-bit RGB)
+ *           become K images of H x W pixels without leaving the device.
+ *
+ * batch:  the ragged CSR layout of K1, K17 and K18: pts [total,3] f64, offsets [B+1] i64 on the DEVICE with offsets[0] = 0
+ *         and offsets[B] <= total; rows at or beyond offsets[B] are neither read nor written.  Empty tiles are legal.
+ * views:  K of them, 1 <= K <= SN_RENDER_MAX_VIEWS, all of H x W pixels.  view_tile [K] i32 (device): view k shows tile
+ *         view_tile[k]; any order; a tile may have no view or several; a value outside 0 .. B-1 shows nothing.
+ *         cam [K,16] f64 (device):  cam[0..11] a 3 x 4 row-major matrix A;  cam[12] kind, 0 orthographic or 1 perspective;
+ *         cam[13] near;  cam[14] far;  cam[15] the point size s in pixels, integral, 1 .. SN_RENDER_MAX_SPLAT.
+ *         A camera row with an unknown kind, a non-integral or out-of-range s, !(near < far), far - near not finite, or
+ *         perspective with near <= 0 shows nothing: its image stays as it was (background after a clearing call) and
+ *         bad_views[k] is set to 1.  Checked on the device, where the cameras live.
+ * rule:   for row j of tile b (j its index in the tile) and every view k with view_tile[k] == b, literally:
+ *
+ *           c_r = ((A[r,0]*x + A[r,1]*y) + A[r,2]*z) + A[r,3]        r = 0, 1, 2   (fp64, every operation rounded once)
+ *           orthographic:  px = c_0, py = c_1, d = c_2
+ *           perspective:   d = c_2;  px = c_0 / d, py = c_1 / d       (true fp64 divisions)
+ *           accepted iff   near <= d < far  and  |px| < 2^30 and |py| < 2^30      (NaN anywhere rejects)
+ *           dq  = min((u64)floor(((d - near) / (far - near)) * 4294967296.0), 2^32 - 1)
+ *           ix  = (i64)floor(px), iy = (i64)floor(py)
+ *           key = (dq << 32) | j
+ *           for every pixel (X, Y) with ix - (s-1)/2 <= X <= ix + s/2, iy - (s-1)/2 <= Y <= iy + s/2   (integer division)
+ *               and 0 <= X < W, 0 <= Y < H:        keys[k, Y, X] = min(keys[k, Y, X], key)      (unsigned 64-bit)
+ *           if 0 <= ix < W and 0 <= iy < H:        count[k, iy, ix] += 1                         (count nullable, u32)
+ *
+ *         Nearest depth wins; among equal depth quanta the lowest row wins.  Integer minima and sums: the result does not
+ *         depend on scheduling.  Background is the key of all ones; a tile of 2^32 - 1 rows or more is refused on the
+ *         device (nothing of it is drawn and bad_views of its views is set), so no row can produce that key.
+ * pixels: a pixel of view k is FOREGROUND iff its key is not all ones, view_tile[k] is in 0 .. B-1 and the key's low word j
+ *         is below that tile's number of rows (always so for keys sn_render_splat left with the same batch and views);
+ *         every other pixel is background.  The winner is row offsets[view_tile[k]] + j of the packed batch.
+ * ------------------------------------------------------------------------- */
+#define SN_RENDER_MAX_VIEWS 64
+#define SN_RENDER_MAX_SPLAT 9
+#define SN_RENDER_ACCUMULATE 1   /* flags: composite onto what keys / count / bad_views hold */
+#define SN_RENDER_NO_LOOK 2      /* flags: send every atomic without looking at the pixel first (same result; for timing) */
+#define SN_RENDER_LOOK_ALWAYS 4  /* flags: look at the pixel first at every point size, 1 included (same result; for timing) */
+#define SN_RENDER_RGB16 0        /* mode: the high bytes of the winner's rgb16 row */
+#define SN_RENDER_DEPTH 1        /* mode: the grey 255 - (dq >> 24) */
+
+/* Rows per workgroup of sn_render_splat (256): host only -- lets a test put its tile sizes on the seams. */
+int sn_render_chunk_points(void);
+
+/* keys [K,H,W] u64, count [K,H,W] u32 (nullable), bad_views [K] i32.  Without SN_RENDER_ACCUMULATE in `flags` one kernel
+ * (no memset node) first sets keys to all ones and zeroes count and bad_views; with it the call composites onto what the
+ * three hold -- how a second layer (tower centroids as 9-pixel splats) goes over a scan.  Then ONE pass over the rows: one
+ * thread owns one row, reads it once and walks the views of its tile; the rows a workgroup works on at a time belong to one
+ * tile, so the view tests are uniform.  Each pixel of a splat of s >= 2 is looked at with a relaxed agent-scope load, and the
+ * 64-bit atomic min is sent only where the look shows more than the row's key; at s = 1 the atomic is sent without a look,
+ * which measured faster (SN_RENDER_NO_LOOK never looks, SN_RENDER_LOOK_ALWAYS always does; the result is the same).  Vector
+ * stores and integer atomics only; no allocation, no synchronisation: capturable.  cam, view_tile, offsets and pts are device
+ * memory: a replay follows their current contents.
+ * SN_ERR_INVALID_ARG: a null pts / offsets / cam / view_tile / keys / bad_views, total, B, K, H or W <= 0, unknown flags or
+ * both look flags, pts / offsets / cam / keys not 8-byte or view_tile / count / bad_views not 4-byte aligned;  SN_ERR_UNSUPPORTED: K >
+ * SN_RENDER_MAX_VIEWS, H * W >= 2^31, total > 2^33, B > 65536.  All checked before any launch. */
+int sn_render_splat(const double* pts, const int64_t* offsets, int64_t total, int B, const double* cam,
+                    const int32_t* view_tile, int K, int H, int W, int flags, uint64_t* keys, uint32_t* count,
+                    int32_t* bad_views, sn_stream_t stream);
+
+/* keys -> pixels: one launch, one thread per pixel.  offsets and view_tile are the splat's.
+ *   rgba    [K,H,W,4] u8: a foreground pixel takes, in SN_RENDER_RGB16 mode, the HIGH byte of each channel of the winner's
+ *           row of rgb16 [total,3] u16 (the inverse of K16's and K18's `* 257`), in SN_RENDER_DEPTH mode the grey
+ *           255 - (dq >> 24) (rgb16 may be null); alpha is 255.  A background pixel takes the four bytes of `background`
+ *           (r in the low byte, then g, b, a).
+ *   index   [K,H,W] i64 (nullable): the winner's row in the packed batch, -1 for background -- the pick buffer.
+ *   depth_q [K,H,W] u32 (nullable): dq; 2^32 - 1 for background.
+ *   edl     f64, finite and >= 0; 0 turns shading off.  For a foreground pixel o = the sum over its up / down / left / right
+ *           neighbours inside the image of max(0, dq_c - dq_n) as a 64-bit integer, dq_n the high word of the neighbour's
+ *           key whatever it is (2^32 - 1 for a background neighbour, which so contributes nothing);
+ *           shade = 1.0 / (1.0 + edl * ((double)o / 4294967296.0)) and every colour channel c becomes
+ *           (u8)floor(c * shade + 0.5), the products, sums and quotients rounded once each.  A pixel with nearer neighbours
+ *           is darkened.  No transcendental: numpy gives the same bits.
+ * No allocation, no synchronisation: capturable.
+ * SN_ERR_INVALID_ARG: a null keys / offsets / view_tile / rgba, B, K, H or W <= 0, an unknown mode, SN_RENDER_RGB16 without
+ * rgb16, edl < 0, NaN or infinite, keys / offsets / index not 8-byte, view_tile / depth_q / rgba not 4-byte or rgb16 not
+ * 2-byte aligned;  SN_ERR_UNSUPPORTED: K > SN_RENDER_MAX_VIEWS, H * W >= 2^31, B > 65536. */
+int sn_render_resolve(const uint64_t* keys, int K, int H, int W, const int64_t* offsets, int B, const int32_t* view_tile,
+                      const uint16_t* rgb16, int mode, uint32_t background, double edl, uint8_t* rgba, int64_t* index,
+                      uint32_t* depth_q, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@ from .voxel_classes import (ClassColors, VoxelClasses, class_colors, classes_on_
 from .neighbours import (PointNeighbours, avg_dist_points, k_distance_curve, knn_distances, point_spacing,
                          remove_outliers)
 from .shapes import PointShapes, estimate_normals, select_by_shape, shape_colors, shape_features
+from .render import (RenderedViews, default_class_table, ortho_camera, perspective_camera, png_bytes, render_points,
+                     render_pred_vs_gt, render_scan, render_voxelgrid, write_png)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalLoss, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss,
                          GENEO_Loss, GENEO_Tversky_Loss, IoULoss, QuantileGENEOLoss, QuantileLoss, TverskyLoss, WeightedMSE)
 
@@ -60,6 +62,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "VoxelClasses", "ClassColors", "voxel_classes", "classes_on_voxel", "class_colors", "color_pointcloud",
            "random_class_colors", "PointNeighbours", "knn_distances", "point_spacing", "k_distance_curve", "remove_outliers",
            "avg_dist_points", "PointShapes", "shape_features", "estimate_normals", "select_by_shape", "shape_colors",
+           "RenderedViews", "ortho_camera", "perspective_camera", "render_points", "render_scan", "render_voxelgrid",
+           "render_pred_vs_gt", "png_bytes", "write_png", "default_class_table",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE", "QuantileLoss", "QuantileGENEOLoss", "FocalLoss", "IoULoss"]

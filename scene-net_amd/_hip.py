@@ -165,6 +165,9 @@ SYMBOLS = {
                                 ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "sn_shape_points_launches": (c_int, [_P, _P, ctypes.c_int64, _I, ctypes.c_double, _I, _I, _P, _I, _I, _I, ctypes.c_int64,
                                          _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sn_render_chunk_points": (c_int, []),
+    "sn_render_splat": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sn_render_resolve": (c_int, [_P, _I, _I, _I, _P, _I, _P, _P, _I, ctypes.c_uint32, ctypes.c_double, _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -187,6 +190,9 @@ SN_CLASS_WORDS, SN_VOXEL_CLASSES_NO_SKIP = 2048, 1
 SN_MERGE_MAX, SN_MERGE_MEAN, SN_MERGE_INTERIOR = 0, 1, 2
 SN_KNN_MAX_K, SN_KNN_NSTAT, SN_KNN_LAUNCHES, SN_KNN_EXCLUDE_ZERO = 16, 5, 4, 1
 SN_SHAPE_SWEEPS, SN_SHAPE_NFEAT, SN_SHAPE_LAUNCHES = 4, 6, 5
+SN_RENDER_MAX_VIEWS, SN_RENDER_MAX_SPLAT = 64, 9
+SN_RENDER_ACCUMULATE, SN_RENDER_NO_LOOK, SN_RENDER_LOOK_ALWAYS = 1, 2, 4
+SN_RENDER_RGB16, SN_RENDER_DEPTH = 0, 1
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -2237,3 +2243,60 @@ def shape_points(pts: torch.Tensor, offsets: torch.Tensor, radius: float, min_po
     else:
         rc = load().sn_shape_points_launches(*head, int(launches[0]), int(launches[1]), _stream())
     _check(rc, "sn_shape_points")
+
+
+# --------------------------------------------------------------------------- #
+def render_chunk_points() -> int:
+    """sn_render_chunk_points: rows per workgroup of the splat kernel (host only)."""
+    return int(load().sn_render_chunk_points())
+
+
+@_on_tensor_device
+def render_splat(pts: torch.Tensor, offsets: torch.Tensor, cam: torch.Tensor, view_tile: torch.Tensor, size: Sequence[int],
+                 keys: torch.Tensor, count: Optional[torch.Tensor], bad_views: torch.Tensor, accumulate: bool = False,
+                 look: Optional[bool] = None) -> None:
+    """sn_render_splat: pts [total,3] f64, offsets [B+1] i64, cam [K,16] f64, view_tile [K] i32, size (H, W) -> keys [K,H,W]
+    (int64 storage of the u64 keys), count [K,H,W] i32 | None (the u32 counts), bad_views [K] i32, all caller-owned.
+    accumulate: composite onto what they hold.  look: None looks at a pixel before the atomic where the point size is >= 2,
+    True at every size, False at none (same result; for timing).  No allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [total, 3] (got {tuple(pts.shape)})")
+    total, B = int(pts.shape[0]), int(offsets.numel()) - 1
+    H, W = (int(v) for v in size)
+    if cam.dim() != 2 or cam.shape[1] != 16:
+        raise HipLibraryError(f"cam must be [K, 16] (got {tuple(cam.shape)})")
+    K = int(cam.shape[0])
+    if view_tile.numel() != K or bad_views.numel() != K:
+        raise HipLibraryError(f"view_tile and bad_views must hold K = {K} entries")
+    if keys.numel() != K * H * W or (count is not None and count.numel() != K * H * W):
+        raise HipLibraryError(f"keys and count must hold K * H * W = {K * H * W} pixels")
+    flags = (SN_RENDER_ACCUMULATE if accumulate else 0) | (0 if look is None else SN_RENDER_LOOK_ALWAYS if look else SN_RENDER_NO_LOOK)
+    rc = load().sn_render_splat(_ptr(pts, torch.float64, "pts"), _ptr(offsets, torch.int64, "offsets"), total, B,
+                                _ptr(cam, torch.float64, "cam"), _ptr(view_tile, torch.int32, "view_tile"), K, H, W, flags,
+                                _ptr(keys, torch.int64, "keys"), _ptr(count, torch.int32, "count"),
+                                _ptr(bad_views, torch.int32, "bad_views"), _stream())
+    _check(rc, "sn_render_splat")
+
+
+@_on_tensor_device
+def render_resolve(keys: torch.Tensor, size: Sequence[int], offsets: torch.Tensor, view_tile: torch.Tensor,
+                   rgb16: Optional[torch.Tensor], mode: int, background: Sequence[int], edl: float, rgba: torch.Tensor,
+                   index: Optional[torch.Tensor] = None, depth_q: Optional[torch.Tensor] = None) -> None:
+    """sn_render_resolve on the keys sn_render_splat left: -> rgba [K,H,W,4] u8, index [K,H,W] i64 | None, depth_q [K,H,W]
+    i32 | None (the u32 quanta), caller-owned.  rgb16 [total,3] u16 (int16 storage serves; None in SN_RENDER_DEPTH mode);
+    background (r, g, b, a) bytes.  No allocation, no synchronisation."""
+    H, W = (int(v) for v in size)
+    K, B = int(view_tile.numel()), int(offsets.numel()) - 1
+    if keys.numel() != K * H * W or rgba.numel() != 4 * K * H * W:
+        raise HipLibraryError(f"keys must hold K * H * W = {K * H * W} pixels and rgba four bytes for each")
+    if any(t is not None and t.numel() != K * H * W for t in (index, depth_q)):
+        raise HipLibraryError(f"index and depth_q must hold K * H * W = {K * H * W} pixels")
+    bg = [int(v) for v in background]
+    if len(bg) != 4 or any(v < 0 or v > 255 for v in bg):
+        raise HipLibraryError(f"background must be four bytes (r, g, b, a) (got {tuple(background)})")
+    rc = load().sn_render_resolve(_ptr(keys, torch.int64, "keys"), K, H, W, _ptr(offsets, torch.int64, "offsets"), B,
+                                  _ptr(view_tile, torch.int32, "view_tile"), _u16_ptr(rgb16, "rgb16"), int(mode),
+                                  bg[0] | (bg[1] << 8) | (bg[2] << 16) | (bg[3] << 24), float(edl),
+                                  _ptr(rgba, torch.uint8, "rgba"), _ptr(index, torch.int64, "index"),
+                                  _ptr(depth_q, torch.int32, "depth_q"), _stream())
+    _check(rc, "sn_render_resolve")
