@@ -249,6 +249,21 @@ int sn_conv_bank_prepared(const void* x, int x_dtype, const float* bank, const f
 int sn_conv_bank_prepared_served(const void* x, int x_dtype, const float* bank, const float* lambdas, void* prep,
                                  int B, int Z, int X, int Y, int G, int kz, int kx, int ky,
                                  void* act, void* out, int out_dtype, sn_stream_t stream);
+/* sn_conv_bank_prepared (assume_served = 0) / _served (1) with the occupancy's ROW BITS: rows[b][z][w] uint32, w < ceil(X / 32),
+ * bit x % 32 of word x / 32 set iff x[b, 0, z, x, :] holds a set voxel (a SUPERSET is allowed and costs time only; a missing
+ * bit is a wrong result: hand in only bits that describe x as it is now).  sn_voxel_occupancy_fused_rows writes them.  rows =
+ * NULL: exactly the two entries above.  With bits, the head-only z-walk of a grid with Y <= 64, Z <= 64, X <= 64 whose launch
+ * has one workgroup per 8-row column (B ceil(X / 8) = the device's compute units) cuts the columns into four z segments where
+ * Z = 64 (option "conv_i8z_segments" = 0; else the count it names, which must divide Z) and deals each tile's segments over
+ * that tile's workgroups by cost (csrc/conv_i8z.inc, THE BALANCED DEAL): same results bit for bit.  Any other launch --
+ * another batch size, 128^3, the activations form -- takes the plan it takes without bits, segment count included, and does
+ * not read them: the gain is confined to one batch size per grid and device.
+ * plan_out (nullable, diagnostics; the caller sizes it by the device's compute units): int32 [compute units][65], row w = (n, the n job numbers of workgroup w in its order;
+ * job number = segment x B ceil(X / 8) + tile x ceil(X / 8) + column slot), written only where the balanced deal runs. */
+int sn_conv_bank_prepared_rows(const void* x, int x_dtype, const float* bank, const float* lambdas, void* prep,
+                               int B, int Z, int X, int Y, int G, int kz, int kx, int ky,
+                               void* act, void* out, int out_dtype, sn_stream_t stream, int assume_served,
+                               const uint32_t* rows, int32_t* plan_out);
 int sn_conv_prep_verdict_offset(void);
 /* Diagnostics: how many waves of the int8 kernels ever gave up a bounded LDS hand-over spin (must stay 0).  A give-up is
  * not silent: it latches the sticky device status (code 1 / 3, above), and the z-walk overwrites its workgroup's outputs
@@ -435,6 +450,14 @@ int sn_voxel_occupancy_fused(const double* pts, const double* labels, const int6
                              double* bbox, double* desc, uint32_t* bits_ws, void* occ, void* gt_occ, int out_dtype,
                              int32_t* flags, int32_t* dropped, int32_t* counts_ws, int32_t* towers_ws,
                              sn_stream_t stream);
+/* ... which also writes the occupancy's row bits (layout: sn_conv_bank_prepared_rows) into row_bits [B][nz][ceil(nx / 32)]
+ * (nullable).  A tile whose flag goes up is rewritten by the exact fallback to a subset of what the bits describe: its bits
+ * stay a superset. */
+int sn_voxel_occupancy_fused_rows(const double* pts, const double* labels, const int64_t* offsets, int B, int nx, int ny,
+                                  int nz, int regular, const double* keep_labels_host, int n_keep, double* partial_ws,
+                                  double* bbox, double* desc, uint32_t* bits_ws, void* occ, void* gt_occ, int out_dtype,
+                                  int32_t* flags, int32_t* dropped, int32_t* counts_ws, int32_t* towers_ws,
+                                  sn_stream_t stream, uint32_t* row_bits);
 
 /* What sn_voxel_occupancy (fused = 0: a descriptor is given), sn_voxel_occupancy_fused (fused = 1: the tile's own box) or
  * sn_voxel_occupancy_sized (sized = 1) would launch for an (nx, ny, nz) grid with `planes` bitmaps (2 with gt_occ, else 1)
@@ -468,6 +491,13 @@ int sn_voxel_occupancy_fused_bank(const double* pts, const double* labels, const
                                   const float* params, const int32_t* kinds, int G, int kz, int kx, int ky, float* bank,
                                   int32_t* status, float* lambdas, const int32_t* order, int last, float* lambdas_out,
                                   void* prep, sn_stream_t stream);
+int sn_voxel_occupancy_fused_bank_rows(const double* pts, const double* labels, const int64_t* offsets, int B, int nx, int ny,
+                                       int nz, int regular, const double* keep_labels_host, int n_keep, double* partial_ws,
+                                       double* bbox, double* desc, uint32_t* bits_ws, void* occ, void* gt_occ, int out_dtype,
+                                       int32_t* flags, int32_t* dropped, int32_t* counts_ws, int32_t* towers_ws,
+                                       const float* params, const int32_t* kinds, int G, int kz, int kx, int ky, float* bank,
+                                       int32_t* status, float* lambdas, const int32_t* order, int last, float* lambdas_out,
+                                       void* prep, sn_stream_t stream, uint32_t* row_bits);
 
 /* sn_voxel_occupancy_fused in VOXEL-SIZE mode (voxelize_ply with size_x / size_y / size_z, utils/pcd_processing.py:365-367;
  * the mode SemanticKITTI uses, core/datasets/semKITTI.py:453-455): every tile's grid extents follow from its own bounding

@@ -44,6 +44,7 @@ SYMBOLS = {
     "sn_conv_bank_prep": (c_int, [_P, _I, _I, _I, _I, _P, _P]),
     "sn_conv_bank_prepared": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "sn_conv_bank_prepared_served": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "sn_conv_bank_prepared_rows": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
     "sn_conv_prep_verdict_offset": (c_int, []),
     "sn_conv_i8_spin_timeouts": (c_int, [_P]),
     "sn_conv_i8z_round_counts": (c_int, [_P]),
@@ -62,6 +63,10 @@ SYMBOLS = {
     "sn_voxel_occupancy": (c_int, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "sn_voxel_occupancy_fused": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
                                          _P]),
+    "sn_voxel_occupancy_fused_rows": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P,
+                                              _P, _P, _P]),
+    "sn_voxel_occupancy_fused_bank_rows": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P,
+                                                   _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sn_voxel_occupancy_plan": (c_int, [_I] * 11 + [_P]),
     "sn_voxel_occupancy_fused_bank": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P,
                                               _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
@@ -531,15 +536,54 @@ def conv_bank_prep(bank: torch.Tensor, prep: Optional[torch.Tensor] = None) -> t
     return prep
 
 
+ROWS_ATTR = "_sn_row_bits"
+
+
+def row_bits_of(occ: torch.Tensor) -> torch.Tensor:
+    """The row bits of an occupancy [B,1,Z,X,Y] (any dtype; set = non-zero) in plain torch ops: int32 [B, Z, ceil(X / 32)],
+    bit x % 32 of word x / 32 set iff occ[b, 0, z, x, :] holds a set voxel (include/scenenet_hip.h,
+    sn_conv_bank_prepared_rows).  No synchronisation; usable inside a graph capture."""
+    B, _, Z, X, _ = occ.shape
+    wx = (X + 31) // 32
+    any_y = (occ[:, 0] != 0).any(dim=-1)                                        # [B, Z, X]
+    if wx * 32 != X:
+        any_y = torch.nn.functional.pad(any_y, (0, wx * 32 - X))
+    shifts = torch.arange(32, dtype=torch.int64, device=occ.device)            # (made on the device: no copy, no sync)
+    v = (any_y.reshape(B, Z, wx, 32).to(torch.int64) << shifts).sum(dim=-1)
+    return torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32).contiguous()
+
+
+def attach_rows(occ: torch.Tensor, rows: torch.Tensor) -> None:
+    """The voxel stage's note on the occupancy tensor it returns: the bits, and what `occ` was when they were made"""
+    setattr(occ, ROWS_ATTR, (rows, occ._version, occ.data_ptr(), tuple(occ.shape)))
+
+
+def rows_for(x: torch.Tensor) -> Optional[torch.Tensor]:
+    """The row bits attached to THIS tensor object, if it has not been written since (same version counter, storage and
+    shape) and they live on its device; else None -- a missing bit would be a silently wrong result, a missing tensor of
+    bits only costs time."""
+    note = getattr(x, ROWS_ATTR, None)
+    if note is None:
+        return None
+    rows, version, ptr, shape = note
+    if x._version != version or x.data_ptr() != ptr or tuple(x.shape) != shape or rows.device != x.device:
+        return None
+    return rows
+
+
 @_on_tensor_device
 def conv_bank(x: torch.Tensor, bank: torch.Tensor, lambdas: Optional[torch.Tensor], want_act: bool = False,
               want_out: bool = True, out_dtype: Optional[torch.dtype] = None, prep: Optional[torch.Tensor] = None,
-              assume_served: bool = False):
+              assume_served: bool = False, row_bits: Optional[torch.Tensor] = None,
+              plan_out: Optional[torch.Tensor] = None):
     """x [B,1,Z,X,Y] (f32|f64|u8|bool), bank [G,kz,kx,ky] f32, lambdas [G] f32 (effective) ->
     (act [B,G,Z,X,Y] | None, out [B,1,Z,X,Y] | None) of out_dtype (sn_conv_bank; with `prep` = conv_bank_prep(bank):
     sn_conv_bank_prepared -- same results bit for bit, the per-bank work not repeated; `assume_served`: the caller has
     read the blob's verdict as 0 for these weights / coefficients / tolerance / outputs: sn_conv_bank_prepared_served, no
-    fallback launch -- see PreparedVerdict)."""
+    fallback launch -- see PreparedVerdict).  With `prep`, the occupancy's row bits travel to the z-walk's balanced deal
+    (sn_conv_bank_prepared_rows): `row_bits` as given (the caller vouches that they describe x: row_bits_of), else the ones
+    the voxel stage left on this very tensor -- taken only while x is still what they were made for (rows_for).  plan_out:
+    int32 [compute units, 65], receives the deal (diagnostics)."""
     if x.dim() != 5 or x.shape[1] != 1:
         raise HipLibraryError(f"x must be [B,1,Z,X,Y] (got {tuple(x.shape)})")
     if x.dtype not in _DT or x.dtype == torch.bfloat16:
@@ -553,12 +597,21 @@ def conv_bank(x: torch.Tensor, bank: torch.Tensor, lambdas: Optional[torch.Tenso
     if prep is not None:
         if prep.dtype != torch.uint8 or prep.numel() < SN_CONV_PREP_BYTES * ((G + 15) // 16):
             raise HipLibraryError("prep: not a blob of conv_bank_prep for this bank")
-        fn = load().sn_conv_bank_prepared_served if assume_served else load().sn_conv_bank_prepared
-        rc = fn(_ptr(x, None, "x"), _DT[x.dtype], _ptr(bank, torch.float32, "bank"),
-                _ptr(lambdas, torch.float32, "lambdas"), _ptr(prep, torch.uint8, "prep"),
-                B, Z, X, Y, G, kz, kx, ky, _ptr(act, None, "act"), _ptr(out, None, "out"),
-                _DT_OUT[out_dtype], _stream())
-        _check(rc, "sn_conv_bank_prepared")
+        rows = row_bits if row_bits is not None else rows_for(x)
+        if rows is not None and (rows.dtype != torch.int32 or rows.device != x.device or not rows.is_contiguous()
+                                 or tuple(rows.shape) != (B, Z, (X + 31) // 32)):
+            raise HipLibraryError("row_bits: int32 [B, Z, ceil(X / 32)] on x's device")
+        if plan_out is not None:   # (the launch writes row blockIdx.x of [compute units][65])
+            cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+            if plan_out.dtype != torch.int32 or plan_out.device != x.device or plan_out.numel() < 65 * cus:
+                raise HipLibraryError(f"plan_out: int32 on x's device with at least {cus} x 65 words")
+        rc = load().sn_conv_bank_prepared_rows(
+            _ptr(x, None, "x"), _DT[x.dtype], _ptr(bank, torch.float32, "bank"),
+            _ptr(lambdas, torch.float32, "lambdas"), _ptr(prep, torch.uint8, "prep"),
+            B, Z, X, Y, G, kz, kx, ky, _ptr(act, None, "act"), _ptr(out, None, "out"),
+            _DT_OUT[out_dtype], _stream(), int(bool(assume_served)), _ptr(rows, torch.int32, "row_bits"),
+            _ptr(plan_out, torch.int32, "plan_out"))
+        _check(rc, "sn_conv_bank_prepared_rows")
         return act, out
     rc = load().sn_conv_bank(_ptr(x, None, "x"), _DT[x.dtype], _ptr(bank, torch.float32, "bank"),
                              _ptr(lambdas, torch.float32, "lambdas"), B, Z, X, Y, G, kz, kx, ky,
@@ -882,7 +935,7 @@ def voxel_occupancy(pts, labels, offsets, desc, n_xyz, keep_labels: Sequence[flo
 @_on_tensor_device
 def voxel_occupancy_fused(pts, labels, offsets, n_xyz, regular: bool = True, keep_labels: Sequence[float] = (),
                           want_gt_occ: bool = False, out_dtype: torch.dtype = torch.uint8, exact_fallback: bool = True,
-                          want_bbox: bool = False, bank_rider=None):
+                          want_bbox: bool = False, bank_rider=None, want_rows: bool = False):
     """sn_voxel_occupancy_fused: bbox + descriptor + LDS-bitmap occupancy in four launches.  Returns
     (occ, gt_occ | None, flags, dropped, desc, bbox | None).  bank_rider = (params [G, SN_NPARAM] f32, kinds [G] i32,
     bank [G,9,9,9] f32 out, prep uint8 out): K2 and the int8 contraction's preparation ride in the first launch
@@ -909,12 +962,15 @@ def voxel_occupancy_fused(pts, labels, offsets, n_xyz, regular: bool = True, kee
               _ptr(offsets, torch.int64, "offsets"), B, nx, ny, nz, int(regular), ctypes.cast(keep, c_void_p),
               len(keep_labels) if want_gt_occ else 0, _ptr(partial), _ptr(bbox), _ptr(desc), _ptr(bits), _ptr(occ),
               _ptr(gt_occ), _DT_OUT[out_dtype], _ptr(flags), _ptr(dropped), _ptr(counts), _ptr(towers))
+    rows = torch.empty((B, nz, (nx + 31) // 32), dtype=torch.int32, device=dev) if want_rows else None
     if bank_rider is None:
-        rc = load().sn_voxel_occupancy_fused(*common, _stream())
+        rc = load().sn_voxel_occupancy_fused_rows(*common, _stream(), _ptr(rows))
         _check(rc, "sn_voxel_occupancy_fused")
     else:
-        _check(load().sn_voxel_occupancy_fused_bank(*common, *_rider_args(bank_rider), _stream()),
+        _check(load().sn_voxel_occupancy_fused_bank_rows(*common, *_rider_args(bank_rider), _stream(), _ptr(rows)),
                "sn_voxel_occupancy_fused_bank")
+    if want_rows:   # (want_rows: the occupancy's row bits int32 [B, nz, ceil(nx / 32)] ride on `occ`: attach_rows)
+        attach_rows(occ, rows)
     return occ, gt_occ, flags, dropped, desc, bbox
 
 

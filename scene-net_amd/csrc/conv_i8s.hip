@@ -276,7 +276,7 @@ int conv_occ_i8s(const uint8_t* x, const float* bank, const float* lambdas, int 
 // 1 when this shape is not served here (caller: sn_conv_bank's own kernels).
 int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint8_t* prep, int B, int Z, int X, int Y,
                  int G, int Gtot, int g0, int head, int kz, int kx, int ky, void* act, void* out, int out_dtype,
-                 hipStream_t stream, int assume_served) {
+                 hipStream_t stream, int assume_served, const uint32_t* rows = nullptr, int32_t* plan_out = nullptr) {
     if (ky != 9 || kz != 9 || kx != 9 || Y % 16 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || G > 16) return 1;
     if ((long long)Z * X * Y >= (1ll << 31)) return 1;   // offsets inside a tile are 32-bit in the walk
     if (act && (reinterpret_cast<uintptr_t>(act) & 15)) return 1;
@@ -340,14 +340,31 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
         // and heavy things are local in x; 0 = two dealt segments where the launch is the head-only one (a workgroup drops
         // its dead jobs: conv_i8z.inc, DEAD JOBS), the tile has two columns in x to deal over, a half is at least the ring
         // (Z >= 32) and the search above found nothing better than whole columns.
+        // THE BALANCED DEAL (conv_i8z.inc) of m segments can run: the head-only form with the occupancy's row bits (`rows`,
+        // sn_conv_bank_prepared_rows) for a grid of one y tile, Z <= 64, X <= 64 (what its one wave holds), when the launch has
+        // exactly one workgroup per column (then the nxt workgroups of a tile's columns hold that tile's nxt x m jobs under
+        // the static deal too, whatever the swizzle), m divides Z and a tile has at most kZBalJobs jobs.  The automatic count
+        // is four only where that holds for four and a quarter is at least the ring (Z >= 64): the balanced deal evens out
+        // what four static segments would not.  A launch it cannot run takes the plan it takes without bits, and the bits are
+        // not used.
         const int want = sn::option(sn::kOptConvI8zSegments);
-        const int n = want >= 2 ? want : (want == 0 && !act && z.nxt >= 2 && Z >= 32 && best_seg == 1) ? 2 : 0;
+        auto bal_ok = [&](int m) {
+            return rows && !act && z.nyt == 1 && Z <= 64 && X <= 64 && ncol == cus && m >= 2 && m <= max_seg && Z % m == 0 &&
+                   z.nxt * m <= kZBalJobs;
+        };
+        const int n = want >= 2 ? want
+                      : (want == 0 && !act && z.nxt >= 2 && Z >= 32 && best_seg == 1) ? (Z >= 64 && bal_ok(4) ? 4 : 2) : 0;
         if (n >= 2 && n <= max_seg && (ncol * n + cus - 1) / cus <= kZMaxJobs) {
             best_seg = n;
             z.deal = 1;
             z.deal_shift = z.nxt / n > 1 ? z.nxt / n : 1;
             z.fill_dead = act ? 0 : 1;
+            if (z.fill_dead && bal_ok(n)) z.bal = 1;
         }
+    }
+    if (z.bal) {
+        z.rows = rows;
+        z.plan_out = plan_out;
     }
     z.LZ = (Z + best_seg - 1) / best_seg;
     z.nseg = (Z + z.LZ - 1) / z.LZ;
@@ -358,7 +375,10 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
     const int grid = (int)(njobs < cus ? njobs : cus);
     const int per_wg = (z.njobs + grid - 1) / grid;
     if (per_wg > kZMaxJobs) return 1;
-    if (!division_magic((unsigned)z.PL, (unsigned)(per_wg * z.PL + 64), z.pl_magic)) return 1;
+    // (THE BALANCED DEAL may give one workgroup up to all of a tile's jobs)
+    const int most = z.bal ? z.nxt * z.nseg : per_wg;
+    if (most > kZMaxJobs) return 1;
+    if (!division_magic((unsigned)z.PL, (unsigned)(most * z.PL + 64), z.pl_magic)) return 1;
     z.swizzle = (grid % 8 == 0) ? 1 : 0;
     const size_t lds = lds_bytes_zwalk();
     const size_t lds_4 = lds_bytes(s4), lds_f = fp32k::lds_bytes(cs, false);
@@ -450,7 +470,8 @@ extern "C" int sn_conv_bank_prep(const float* bank, int G, int kz, int kx, int k
 
 static int conv_bank_prepared_impl(const void* x, int x_dtype, const float* bank, const float* lambdas, void* prep,
                                    int B, int Z, int X, int Y, int G, int kz, int kx, int ky, void* act, void* out,
-                                   int out_dtype, sn_stream_t stream, int assume_served) {
+                                   int out_dtype, sn_stream_t stream, int assume_served, const uint32_t* rows = nullptr,
+                                   int32_t* plan_out = nullptr) {
     if (!x || !bank) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_prepared: null x or bank");
     if (!act && !out) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_prepared: both act and out are null");
     if (out && !lambdas) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_prepared: out needs lambdas");
@@ -465,7 +486,8 @@ static int conv_bank_prepared_impl(const void* x, int x_dtype, const float* bank
         const int head = G > 16 ? ((g0 > 0 ? 1 : 0) | (g0 + gc >= G ? 2 : 0)) : 2;
         int rc = sn::conv_occ_i8z((const uint8_t*)x, bank + (size_t)g0 * 729, lambdas ? lambdas + g0 : nullptr,
                                   static_cast<uint8_t*>(prep) + (size_t)(g0 / 16) * SN_CONV_PREP_BYTES, B, Z, X, Y, gc, G,
-                                  g0, head, kz, kx, ky, act, out, out_dtype, sn::as_stream(stream), assume_served);
+                                  g0, head, kz, kx, ky, act, out, out_dtype, sn::as_stream(stream), assume_served, rows,
+                                  plan_out);
         if (rc == 1)   // shape not served by the z-walk: this group through sn_conv_bank's own kernels
             rc = sn::conv_bank_group(x, x_dtype, bank + (size_t)g0 * 729, lambdas ? lambdas + g0 : nullptr, B, Z, X, Y, gc,
                                      G, g0, head, kz, kx, ky, act, out, out_dtype, stream);
@@ -484,6 +506,18 @@ extern "C" int sn_conv_bank_prepared_served(const void* x, int x_dtype, const fl
                                             int B, int Z, int X, int Y, int G, int kz, int kx, int ky, void* act,
                                             void* out, int out_dtype, sn_stream_t stream) {
     return conv_bank_prepared_impl(x, x_dtype, bank, lambdas, prep, B, Z, X, Y, G, kz, kx, ky, act, out, out_dtype, stream, 1);
+}
+
+// ... with the occupancy's row bits (nullable: then exactly the two entries above) and, for tests and tools, the plan the
+// balanced deal made (nullable; [256][65] int32: count, job numbers)
+extern "C" int sn_conv_bank_prepared_rows(const void* x, int x_dtype, const float* bank, const float* lambdas, void* prep,
+                                          int B, int Z, int X, int Y, int G, int kz, int kx, int ky, void* act, void* out,
+                                          int out_dtype, sn_stream_t stream, int assume_served, const uint32_t* rows,
+                                          int32_t* plan_out) {
+    if (rows && (reinterpret_cast<uintptr_t>(rows) & 3))
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_bank_prepared_rows: rows must be 4-byte aligned");
+    return conv_bank_prepared_impl(x, x_dtype, bank, lambdas, prep, B, Z, X, Y, G, kz, kx, ky, act, out, out_dtype, stream,
+                                   assume_served ? 1 : 0, rows, plan_out);
 }
 
 extern "C" int sn_conv_prep_verdict_offset(void) { return kPrepRoute; }

@@ -98,6 +98,10 @@ constexpr int kZYqRow = 256, kZYqPlane = kZRows * kZYqRow;   // 16 lanes x 16 B;
 constexpr int kZYcRow = 64, kZYcPlane = kZRows * kZYcRow + 32;   // 264 dwords: planes 2 apart (lane groups 0/1, 2/3) and
                                                                  // planes -14 apart (ring wrap) are 16 banks apart (mod 32)
 constexpr int kZMaxJobs = 256;                 // jobs per workgroup (job table in LDS)
+// THE BALANCED DEAL: jobs per tile (one lane each), and a job's cost in nanoseconds of the plan model (DESIGN section 4:
+// 0.52 us per plane streamed, 0.122 us per round run; a dead job is its fill, 16 KB .. 64 KB of stores)
+constexpr int kZBalJobs = 64;
+constexpr int kBalPlane = 520, kBalRound = 122, kBalFill = 300;
 // Skip mode only: cut every column into this many z segments and deal segment sg of column xt to the workgroup of column
 // xt + SN_I8Z_SKIP_SHIFT sg, so that a workgroup's work comes from several columns (0: the plan of the dense walk).
 #ifndef SN_I8Z_SKIP_NSEG
@@ -138,6 +142,9 @@ struct ZShape {
     int dense;                    // sn_set_option("conv_i8z_dense"): run every round, whatever its window holds
     int deal, deal_shift;         // jobs in segment-major order, segment sg of column (b, yt, xt) dealt as column xt + shift sg
                                   // (mod nxt): a workgroup's segments come from different columns (SN_I8Z_SKIP_NSEG)
+    int bal;                      // THE BALANCED DEAL: the workgroups of a tile share its jobs by cost, from `rows`
+    const uint32_t* rows;         // the occupancy's row bits [B][Z][ceil(X / 32)] (sn_conv_bank_prepared_rows), bal only
+    int32_t* plan_out;            // nullable, bal only: row blockIdx.x of [grid][1 + kZBalJobs] = (count, job numbers ...)
 };
 
 // diagnostics (sn_conv_i8z_round_counts): rounds the walk ran / skipped (empty operand window), all launches since load
@@ -412,7 +419,14 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     // counters: [0..15] folded[slot]: fold passes of the planes that lived there (4 per plane);
     //           [16..31] read[slot]: tickets of the slots s = slot (mod 16) that are through with their ring reads (kTPS per slot);
     //           [32..95] landed[pass][slot]: LDS-DMA passes arrived;  [96] ticket counter;  [97] asymmetric bank;  [98] a spin gave up
-    //           [99] can_skip;  [100] rounds run, [101] rounds skipped, [102] waves that have added theirs;  [103] live jobs (DEAD JOBS)
+    //           [99] can_skip;  [100] rounds run, [101] rounds skipped, [102] waves that have added theirs;  [103] live jobs (DEAD JOBS;
+    //           THE BALANCED DEAL: the live jobs of this workgroup's share);  [104] THE BALANCED DEAL: jobs in this workgroup's table.
+    //           [103] / [104] are written by wave 0 ahead of the prologue's second barrier and, when the launch may not skip, once
+    //           more by wave 0 behind the verdict (the static table and its count).  `dealt` -- which poison_jobs walks -- is read
+    //           from [104] right behind the second barrier and again behind the __syncthreads that ends the prologue.  A slow
+    //           wave's first read may already see the static count: wave 0 writes it only once it is past the verdict, i.e. in a
+    //           launch that does not decline (the verdict is workgroup-uniform), so no wave poisons with it, no wave requests
+    //           planes early (each finds the same coefficients not finite), and every wave reads it again before it is used.
     int* const ticket_ctr = cnt + 96;
 
 #ifdef SN_CONV_TIMING
@@ -426,7 +440,8 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     SN_ST(0);
     const size_t V = (size_t)zs.Z * zs.X * zs.Y;
     const int grid = (int)gridDim.x;
-    const int dealt = (int)blockIdx.x < zs.njobs ? (zs.njobs - 1 - (int)blockIdx.x) / grid + 1 : 0;   // jobs of this workgroup
+    int dealt = (int)blockIdx.x < zs.njobs ? (zs.njobs - 1 - (int)blockIdx.x) / grid + 1 : 0;   // jobs of this workgroup
+    const int dealt_static = dealt;           // (THE BALANCED DEAL changes `dealt`)
     int my_jobs = dealt;                      // ... and those it walks (DEAD JOBS below: the live ones)
     int NPL = my_jobs * zs.PL;                // planes of this workgroup's stream
     int nslots = NPL + kZD;                   // slots (the last kZD only flush rounds)
@@ -485,8 +500,9 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         const int yc0 = (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)Yc;
         stab[e] = make_int4(yq0 + a * kZYqPlane, yc0 + a * kZYcPlane, yq0 + b * kZYqPlane, yc0 + b * kZYcPlane);
     }
-    if (tid < my_jobs) {
-        int j = zjob_id(zs, (int)blockIdx.x, tid, grid);
+    // job k of this workgroup under the static plan: (b, x0, y0, zs)
+    auto static_job = [&](int k) -> int4 {
+        int j = zjob_id(zs, (int)blockIdx.x, k, grid);
         int xt, yt, sg;
         if (zs.deal) {
             const int ncol = zs.B * zs.nxt * zs.nyt;
@@ -499,10 +515,13 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             yt = j % zs.nyt; j /= zs.nyt;
             sg = j % zs.nseg; j /= zs.nseg;
         }
-        jobtab[tid] = make_int4(j, xt * kZTX, yt * TY, sg * zs.LZ);
-    }
+        return make_int4(j, xt * kZTX, yt * TY, sg * zs.LZ);
+    };
+    if (tid < my_jobs) jobtab[tid] = static_job(tid);
+    // THE BALANCED DEAL (round 9, zs.bal): the job table comes from the tile's row bits, see below; no byte check
+    const bool bal = kLean && fill_dead && zs.bal != 0;
     if constexpr (kLean) {
-        if (fill_dead)
+        if (fill_dead && !bal)
             for (int i = tid; i < kZMaxJobs; i += kNT) live[i] = 0;
     }
     lds_barrier();
@@ -638,8 +657,114 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     auto region_report = [&](int k, uint32_t a) {
         if (__builtin_amdgcn_ballot_w64(a != 0u) != 0ull && lane == 0) live[k] = 1;
     };
+    // THE BALANCED DEAL (round 9, head-only form; host guard in conv_i8s.hip: one y tile, Z <= 64, X <= 64, as many columns
+    // as workgroups, at most kZBalJobs jobs per tile).  The nxt workgroups that the static deal gives one tile's columns share
+    // that tile's nxt x nseg jobs by cost instead.  Every one of them forms the SAME plan from the same 512 bytes -- the tile's
+    // row bits, rows[b][z][w]: bit x % 32 of word x / 32 set iff plane z, row x holds a set voxel (a superset is allowed: it costs
+    // time, never a result) -- in its wave 0, and keeps its share; nothing is exchanged.  Lane z holds plane z's 64 row bits and
+    // their nine-plane window W (the OR over z - 4 .. z + 4); lane jj holds job jj = sg nxt + xs, the static deal's job number
+    // sg ncol + b nxt + xs: column xt = (xs + shift sg) % nxt, planes sg LZ ...  Per column, ballots over the planes give
+    //   live        a row bit in planes zs - 4 .. zs + LZ + 3, rows x0 - 4 .. x0 + 11: DEAD JOBS' rule (one y tile: every y counts)
+    //   rounds_run  the rounds (x-rows h .. h + kH - 1, plane z) with a bit of W[z] in rows h .. h + kH + 7: EMPTY WINDOWS' rule
+    // and  cost = live ? kBalPlane PL + kBalRound rounds_run : kBalFill  (integers: tools/debug/zwalk_balanced_model.py deals
+    // the same).  Jobs in the order (cost descending, job number ascending) go one by one to the workgroup with the smallest
+    // load, ties to the lowest.  A workgroup's table holds its jobs in that order: the live ones come first by themselves (a
+    // live job costs more than any dead one).  The table is written over the static one, which wave 0 restores if the launch may
+    // not skip (then every job is live and the static deal runs, as without bits).
     if constexpr (kLean) {
-        if (fill_dead) {
+        if (bal && wave == 0) {
+            const int nxt = zs.nxt, nj = nxt * zs.nseg;
+            const int c0 = zjob_id(zs, (int)blockIdx.x, 0, grid);   // (ncol == grid: the workgroup's column number)
+            const int b = c0 / nxt, me = c0 - b * nxt;
+            const int wx = (zs.X + 31) >> 5;
+            unsigned long long r = 0ull;
+            if (lane < zs.Z) {
+                const uint32_t* p = zs.rows + ((size_t)b * zs.Z + lane) * wx;
+                r = p[0];
+                if (wx > 1) r |= (unsigned long long)p[1] << 32;
+            }
+            auto up = [&](unsigned long long v, int d) { const unsigned long long t = __shfl_up(v, d, 64); return lane >= d ? t : 0ull; };
+            auto down = [&](unsigned long long v, int d) { const unsigned long long t = __shfl_down(v, d, 64); return lane + d < 64 ? t : 0ull; };
+            const unsigned long long w3 = r | up(r, 1) | down(r, 1);
+            // (w3 of lane z covers planes z - 1 .. z + 1; the lanes three away, CLAMPED to the wave: near an end of the wave the
+            // end lane's two planes are inside the window, and w3 of a lane that does not exist would have held one of them)
+            const unsigned long long W = w3 | __shfl(w3, lane >= 3 ? lane - 3 : 0, 64) | __shfl(w3, lane + 3 < 64 ? lane + 3 : 63, 64);
+            // this lane's job
+            const int sg = lane / nxt, xs = lane - sg * nxt, xt_mine = (xs + zs.deal_shift * sg) % nxt, z0 = sg * zs.LZ;
+            auto zbits = [](int lo, int hi) -> unsigned long long {   // planes lo .. hi - 1, 0 <= lo, hi <= 64
+                if (hi <= lo) return 0ull;
+                return (hi >= 64 ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
+            };
+            const int z1 = z0 + zs.LZ < zs.Z ? z0 + zs.LZ : zs.Z;
+            const unsigned long long zrun = zbits(z0 < 64 ? z0 : 64, z1),
+                                     zreg = zbits(z0 - 4 > 0 ? (z0 - 4 < 64 ? z0 - 4 : 64) : 0, z1 + 4 < zs.Z ? z1 + 4 : zs.Z);
+            bool lv = false;
+            int rounds = 0;
+#pragma unroll 1
+            for (int xt = 0; xt < nxt; ++xt) {
+                const int x0 = xt * kZTX;
+                // halo rows x0 - 4 .. x0 + 11 of this lane's plane: bit i = row x0 - 4 + i (rows outside the grid hold no bit)
+                const uint32_t raw16 = (uint32_t)(x0 >= 4 ? r >> (x0 - 4) : r << 4) & 0xffffu;
+                const uint32_t win16 = (uint32_t)(x0 >= 4 ? W >> (x0 - 4) : W << 4) & 0xffffu;
+                const bool is_mine = xt == xt_mine;
+                const unsigned long long lb = __builtin_amdgcn_ballot_w64(raw16 != 0u);
+                if (is_mine) lv = (lb & zreg) != 0ull;
+                const int nrows = zs.X - x0 < kZTX ? zs.X - x0 : kZTX;
+#pragma unroll
+                for (int h = 0; h < kZTX; h += kH) {
+                    if (h < nrows) {
+                        const unsigned long long rb = __builtin_amdgcn_ballot_w64((win16 & (((1u << (kH + 8)) - 1u) << h)) != 0u);
+                        if (is_mine) rounds += __builtin_popcountll(rb & zrun);
+                    }
+                }
+            }
+            const uint32_t cost = lv ? (uint32_t)(kBalPlane * zs.PL + kBalRound * rounds) : (uint32_t)kBalFill;
+            // rank in (cost descending, job number ascending): keys are distinct, a lane without a job has none
+            const uint32_t key = lane < nj ? cost * 64u + (uint32_t)(63 - lane) : 0u;
+            int rank = 0;
+#pragma unroll 1
+            for (int i = 0; i < nj; ++i) rank += (uint32_t)__builtin_amdgcn_readlane((int)key, i) > key ? 1 : 0;
+            // lane s: the job of rank s
+            uint32_t sk = 0u;
+            if (lane < nj) sk = (uint32_t)__builtin_amdgcn_ds_permute(rank * 4, (int)key);
+            // the deal: lanes 0 .. nxt - 1 hold the workgroups' loads; the smallest (load, workgroup) of the first eight lanes by
+            // three DPP steps (lane ^ 1, lane ^ 2, the other quad of the half row)
+            uint32_t load = lane < nxt ? 0u : 0x0fffffffu;
+            int owner = -1;
+#pragma unroll 1
+            for (int s = 0; s < nj; ++s) {
+                const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)sk, s) >> 6;
+                uint32_t m = (load << 3) | (uint32_t)(lane & 7);
+                uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xf, 0xf, false);
+                m = o < m ? o : m;
+                o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xf, 0xf, false);
+                m = o < m ? o : m;
+                o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xf, 0xf, false);
+                m = o < m ? o : m;
+                const int arg = __builtin_amdgcn_readfirstlane((int)m) & 7;
+                if (lane == arg) load += cs;
+                if (lane == s) owner = arg;
+            }
+            const bool mine = lane < nj && owner == me;
+            const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine);
+            const unsigned long long lvb = __builtin_amdgcn_ballot_w64(mine && (sk >> 6) > (uint32_t)kBalFill);
+            const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
+            const int n_mine = __builtin_popcountll(mb);
+            if (mine) {
+                const int jj = 63 - (int)(sk & 63u);
+                const int jsg = jj / nxt, jxs = jj - jsg * nxt;
+                jobtab[pos] = make_int4(b, ((jxs + zs.deal_shift * jsg) % nxt) * kZTX, 0, jsg * zs.LZ);
+                if (zs.plan_out) zs.plan_out[(size_t)blockIdx.x * (1 + kZBalJobs) + 1 + pos] = jsg * (zs.B * nxt) + b * nxt + jxs;
+            }
+            if (lane == 0) {
+                cnt[103] = __builtin_popcountll(lvb);
+                cnt[104] = n_mine;
+                if (zs.plan_out) zs.plan_out[(size_t)blockIdx.x * (1 + kZBalJobs)] = n_mine;
+            }
+        }
+    }
+    if constexpr (kLean) {
+        if (fill_dead && !bal) {
 #pragma unroll 1
             for (int k = 0; k < dealt; k += 2) {   // (more than two jobs per workgroup: one more latency per pair)
                 uint32_t a0 = 0u, a1 = 0u;
@@ -667,8 +792,30 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     }
     lds_barrier();
     bool early = false;   // fill_dead: the first planes are in flight already (job 0 is live and owns all of them)
+    // (every coefficient finite, scale not negative: what can_skip asks, below)
+    auto coef_finite = [&]() -> bool {
+        bool fin = true;
+        if (lane < 16) {
+            const float sc = scale[lane];
+            const float ls = (out && lane < zs.G) ? lamhi[16 + lane] * sc : 0.0f;
+            const float lh = 65536.0f * ls;
+            auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+            fin = finite(sc) && !(__float_as_uint(sc) >> 31) && finite(ls) && finite(lh);
+        }
+        return __builtin_amdgcn_ballot_w64(!fin) == 0ull;
+    };
+    bool bal_keep = false;   // the balanced table stands (the launch may skip)
     if constexpr (kLean) {
-        if (fill_dead && dealt > 0 && zs.PL >= kZPre && __builtin_amdgcn_readfirstlane(live[0]) != 0) {
+        if (bal) {
+            // the balanced table's first job, if live, stays the first whatever the verdict says -- unless the launch may not
+            // skip (wave 0 then restores the static table, below): every wave looks at the coefficients itself
+            dealt = __builtin_amdgcn_readfirstlane(cnt[104]);
+            bal_keep = coef_finite() && !zs.dense;
+            if (bal_keep && zs.PL >= kZPre && __builtin_amdgcn_readfirstlane(cnt[103]) > 0) {
+                early = true;
+                for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
+            }
+        } else if (fill_dead && dealt > 0 && zs.PL >= kZPre && __builtin_amdgcn_readfirstlane(live[0]) != 0) {
             early = true;   // (npre = kZPre: landed[] above is the stream's, whatever becomes of the other jobs)
             for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
         }
@@ -711,7 +858,20 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         const bool all_fin = __builtin_amdgcn_ballot_w64(!fin) == 0ull;
         if (lane == 0) cnt[99] = (all_fin && !zs.dense) ? 1 : 0;
         if constexpr (kLean) {
-            if (fill_dead) {
+            if (bal) {
+                if (!(all_fin && !zs.dense)) {
+                    // THE BALANCED DEAL, declined: every job is live, the static deal runs (NaN / inf propagate as without bits)
+                    for (int k = lane; k < dealt_static; k += 64) {
+                        jobtab[k] = static_job(k);
+                        if (zs.plan_out) zs.plan_out[(size_t)blockIdx.x * (1 + kZBalJobs) + 1 + k] = zjob_id(zs, (int)blockIdx.x, k, grid);
+                    }
+                    if (lane == 0) {
+                        cnt[103] = dealt_static;
+                        cnt[104] = dealt_static;
+                        if (zs.plan_out) zs.plan_out[(size_t)blockIdx.x * (1 + kZBalJobs)] = dealt_static;
+                    }
+                }
+            } else if (fill_dead) {
                 // DEAD JOBS, the job table: live jobs first, in their order, the dead ones behind them, written by this wave from a copy
                 // it made (a wave's DS operations execute in order).  A launch that may not skip has no dead job.
                 const bool may_skip = all_fin && !zs.dense;
@@ -745,6 +905,9 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (kLean) {
+        if (bal) my_jobs = dealt = __builtin_amdgcn_readfirstlane(cnt[104]);
+    }
     if (my_jobs == 0) return;
     const bool can_skip = __builtin_amdgcn_readfirstlane(cnt[99]) != 0;
     int n_run = 0, n_skip = 0;   // this wave's rounds (scalar)

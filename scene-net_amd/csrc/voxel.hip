@@ -962,7 +962,8 @@ __global__ __launch_bounds__(kThreads) void occ_finalize_kernel(const uint32_t* 
                                                                 const int32_t* __restrict__ dropped_parts,
                                                                 int32_t* __restrict__ dropped,
                                                                 const int32_t* __restrict__ dims, int nx,
-                                                                unsigned long long* __restrict__ exchange_slots) {
+                                                                unsigned long long* __restrict__ exchange_slots,
+                                                                uint32_t* __restrict__ row_bits) {
     const int b = blockIdx.y;
     // (the one-pass kernel's exchange tags of this tile: zeroed here, behind that launch, so that a replayed graph --
     // whose launches carry the same tag every time -- never finds the previous replay's)
@@ -988,6 +989,13 @@ __global__ __launch_bounds__(kThreads) void occ_finalize_kernel(const uint32_t* 
     // DESIGN K1).  The emptiness proof of a row rides on the merged words: inside the thread for rows of <= 4 words, by
     // shuffles over the row's lanes for longer rows (then every lane of a row group runs the same trips: words % 256 == 0).
     const bool vec4 = SN_OCC_VEC4(words, ((uintptr_t)bits_ws & 15) == 0, fused_proof, wpr);
+    // ROW BITS (row_bits, nullable): rows[b][z][w], w < ceil(nx / 32): bit x % 32 of word x / 32 set iff row (z, x) holds a set
+    // voxel of the occupancy plane -- what the contraction's balanced deal plans from (sn_conv_bank_prepared_rows).  With
+    // rows of two words and nx a multiple of 32 they ride on the merged words: a thread holds rows 2 q and 2 q + 1, which are
+    // bits 2 (q % 16), + 1 of word q / 16; sixteen lanes OR theirs together (rows / 2 is a multiple of 16: the sixteen run the
+    // same trips).  Any other layout: a pass of its own behind the loops.
+    const int rows_wx = (nx + 31) >> 5;
+    const bool rows_fused = row_bits && vec4 && wpr == 2 && (nx & 31) == 0;
     if (vec4) {
         const int words4 = words >> 2;
         for (int q = gtid; q < words4; q += gstride) {
@@ -1015,6 +1023,14 @@ __global__ __launch_bounds__(kThreads) void occ_finalize_kernel(const uint32_t* 
                     empty |= (any == 0u);
                 }
             }
+            if (rows_fused) {
+                uint32_t rb = ((((m.x | m.y) != 0u) ? 1u : 0u) | (((m.z | m.w) != 0u) ? 2u : 0u)) << (2 * (threadIdx.x & 15));
+                rb |= __shfl_xor(rb, 1, 64);
+                rb |= __shfl_xor(rb, 2, 64);
+                rb |= __shfl_xor(rb, 4, 64);
+                rb |= __shfl_xor(rb, 8, 64);
+                if ((threadIdx.x & 15) == 0) row_bits[(size_t)b * (rows >> 5) + (q >> 4)] = rb;
+            }
         }
     } else
     for (int w = gtid; w < words; w += gstride) {
@@ -1025,6 +1041,26 @@ __global__ __launch_bounds__(kThreads) void occ_finalize_kernel(const uint32_t* 
             uint32_t any = m0;
             for (int o = wpr >> 1; o > 0; o >>= 1) any |= __shfl_xor(any, o, 64);
             empty |= (any == 0u);
+        }
+    }
+    if (row_bits && !rows_fused) {
+        const int nzz = rows / (nx > 0 ? nx : 1);
+        for (int i = gtid; i < nzz * rows_wx; i += gstride) {
+            const int z = i / rows_wx, xw = i - z * rows_wx;
+            uint32_t rb = 0u;
+            for (int x = 32 * xw; x < nx && x < 32 * xw + 32; ++x) {
+                const long lo = ((long)z * nx + x) * ny, hi = lo + ny;
+                uint32_t any = 0u;
+                for (long w = lo >> 5; w <= (hi - 1) >> 5; ++w) {
+                    uint32_t m = merged_word(src, parts, planes, words, 0, w);
+                    const long wlo = w << 5;
+                    if (lo > wlo) m &= ~0u << (lo - wlo);
+                    if (hi < wlo + 32) m &= ~0u >> (wlo + 32 - hi);
+                    any |= m;
+                }
+                rb |= (any != 0u ? 1u : 0u) << (x & 31);
+            }
+            row_bits[(size_t)b * nzz * rows_wx + i] = rb;
         }
     }
     if (!flags) return;
@@ -1461,7 +1497,7 @@ static int occupancy_impl(const double* pts, const double* labels, const int64_t
                           void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped, int32_t* counts_ws,
                           int32_t* towers_ws, const double* box_parts, int nbparts, int regular, double* bbox_out,
                           sn_stream_t stream, const int32_t* dims = nullptr, const BankRider* onepass_rider = nullptr,
-                          bool onepass = false) {
+                          bool onepass = false, uint32_t* row_bits = nullptr) {
     if (!pts || !offsets || !desc || !bits_ws || !occ)
         return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy: null pointer");
     if (B <= 0 || nx <= 0 || ny <= 0 || nz <= 0)
@@ -1518,10 +1554,10 @@ static int occupancy_impl(const double* pts, const double* labels, const int64_t
     if (out_dtype == SN_U8)
         hipLaunchKernelGGL(occ_finalize_kernel<uint8_t>, dim3(C, B), dim3(kThreads), 0, s, bits_ws, words, planes,
                            parts, rows, ny, V, (uint8_t*)occ, (uint8_t*)gt_occ, flags, dropped_parts, dropped, dims, nx,
-                           exchange);
+                           exchange, row_bits);
     else
         hipLaunchKernelGGL(occ_finalize_kernel<float>, dim3(C, B), dim3(kThreads), 0, s, bits_ws, words, planes, parts,
-                           rows, ny, V, (float*)occ, (float*)gt_occ, flags, dropped_parts, dropped, dims, nx, exchange);
+                           rows, ny, V, (float*)occ, (float*)gt_occ, flags, dropped_parts, dropped, dims, nx, exchange, row_bits);
     // flagged tiles (a y column might be full): redone exactly by one gated launch
     if (flags && counts_ws) {
         const size_t lds3 = (size_t)ne * sizeof(double) + (size_t)ny * sizeof(int);
@@ -1546,11 +1582,11 @@ extern "C" int sn_voxel_occupancy(const double* pts, const double* labels, const
                           stream);
 }
 
-extern "C" int sn_voxel_occupancy_fused(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
-                                        int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
-                                        double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
-                                        void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
-                                        int32_t* counts_ws, int32_t* towers_ws, sn_stream_t stream) {
+static int occupancy_fused_impl(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
+                                int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
+                                double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
+                                void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
+                                int32_t* counts_ws, int32_t* towers_ws, sn_stream_t stream, uint32_t* row_bits) {
     if (!pts || !offsets || !partial_ws || !desc)
         return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy_fused: null pointer");
     if (B <= 0 || nx <= 0 || ny <= 0 || nz <= 0)
@@ -1568,7 +1604,27 @@ extern "C" int sn_voxel_occupancy_fused(const double* pts, const double* labels,
     }
     return occupancy_impl(pts, labels, offsets, B, desc, nx, ny, nz, keep_labels_host, n_keep, bits_ws, occ, gt_occ,
                           out_dtype, flags, dropped, counts_ws, towers_ws, partial_ws, SN_BBOX_PARTS, regular ? 1 : 0,
-                          bbox, stream, nullptr, nullptr, one);
+                          bbox, stream, nullptr, nullptr, one, row_bits);
+}
+
+extern "C" int sn_voxel_occupancy_fused(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
+                                        int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
+                                        double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
+                                        void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
+                                        int32_t* counts_ws, int32_t* towers_ws, sn_stream_t stream) {
+    return occupancy_fused_impl(pts, labels, offsets, B, nx, ny, nz, regular, keep_labels_host, n_keep, partial_ws, bbox, desc,
+                                bits_ws, occ, gt_occ, out_dtype, flags, dropped, counts_ws, towers_ws, stream, nullptr);
+}
+
+// ... and the occupancy's row bits (row_bits [B][nz][ceil(nx / 32)] uint32, nullable: occ_finalize_kernel, ROW BITS)
+extern "C" int sn_voxel_occupancy_fused_rows(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
+                                             int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
+                                             double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
+                                             void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
+                                             int32_t* counts_ws, int32_t* towers_ws, sn_stream_t stream,
+                                             uint32_t* row_bits) {
+    return occupancy_fused_impl(pts, labels, offsets, B, nx, ny, nz, regular, keep_labels_host, n_keep, partial_ws, bbox, desc,
+                                bits_ws, occ, gt_occ, out_dtype, flags, dropped, counts_ws, towers_ws, stream, row_bits);
 }
 
 extern "C" int sn_voxel_occupancy_plan(int nx, int ny, int nz, int planes, int B, int fused, int sized, int pts_aligned16,
@@ -1621,14 +1677,14 @@ static void launch_bbox_with_riders(const double* pts, const int64_t* offsets, d
                            r);
 }
 
-extern "C" int sn_voxel_occupancy_fused_bank(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
-                                             int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
-                                             double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
-                                             void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
-                                             int32_t* counts_ws, int32_t* towers_ws, const float* params,
-                                             const int32_t* kinds, int G, int kz, int kx, int ky, float* bank,
-                                             int32_t* status, float* lambdas, const int32_t* order, int last,
-                                             float* lambdas_out, void* prep, sn_stream_t stream) {
+static int occupancy_fused_bank_impl(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
+                                     int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
+                                     double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
+                                     void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
+                                     int32_t* counts_ws, int32_t* towers_ws, const float* params,
+                                     const int32_t* kinds, int G, int kz, int kx, int ky, float* bank,
+                                     int32_t* status, float* lambdas, const int32_t* order, int last,
+                                     float* lambdas_out, void* prep, sn_stream_t stream, uint32_t* row_bits) {
     if (!pts || !offsets || !partial_ws || !desc)
         return sn::fail(SN_ERR_INVALID_ARG, "sn_voxel_occupancy_fused_bank: null pointer");
     if (B <= 0 || nx <= 0 || ny <= 0 || nz <= 0)
@@ -1642,14 +1698,41 @@ extern "C" int sn_voxel_occupancy_fused_bank(const double* pts, const double* la
                           16 * ((G + 15) / 16) + (lambdas ? 1 : 0)};
         return occupancy_impl(pts, labels, offsets, B, desc, nx, ny, nz, keep_labels_host, n_keep, bits_ws, occ, gt_occ,
                               out_dtype, flags, dropped, counts_ws, towers_ws, partial_ws, SN_BBOX_PARTS, regular ? 1 : 0,
-                              bbox, stream, nullptr, &r, true);
+                              bbox, stream, nullptr, &r, true, row_bits);
     }
     launch_bbox_with_riders(pts, offsets, partial_ws, B, params, kinds, G, bank, status, lambdas, order, last, lambdas_out,
                             prep, sn::as_stream(stream));
     if (int rc = sn::check_launch("sn_voxel_occupancy_fused_bank(bbox + bank)")) return rc;
     return occupancy_impl(pts, labels, offsets, B, desc, nx, ny, nz, keep_labels_host, n_keep, bits_ws, occ, gt_occ,
                           out_dtype, flags, dropped, counts_ws, towers_ws, partial_ws, SN_BBOX_PARTS, regular ? 1 : 0,
-                          bbox, stream);
+                          bbox, stream, nullptr, nullptr, false, row_bits);
+}
+
+extern "C" int sn_voxel_occupancy_fused_bank(const double* pts, const double* labels, const int64_t* offsets, int B, int nx,
+                                             int ny, int nz, int regular, const double* keep_labels_host, int n_keep,
+                                             double* partial_ws, double* bbox, double* desc, uint32_t* bits_ws, void* occ,
+                                             void* gt_occ, int out_dtype, int32_t* flags, int32_t* dropped,
+                                             int32_t* counts_ws, int32_t* towers_ws, const float* params,
+                                             const int32_t* kinds, int G, int kz, int kx, int ky, float* bank,
+                                             int32_t* status, float* lambdas, const int32_t* order, int last,
+                                             float* lambdas_out, void* prep, sn_stream_t stream) {
+    return occupancy_fused_bank_impl(pts, labels, offsets, B, nx, ny, nz, regular, keep_labels_host, n_keep, partial_ws, bbox,
+                                     desc, bits_ws, occ, gt_occ, out_dtype, flags, dropped, counts_ws, towers_ws, params, kinds,
+                                     G, kz, kx, ky, bank, status, lambdas, order, last, lambdas_out, prep, stream, nullptr);
+}
+
+extern "C" int sn_voxel_occupancy_fused_bank_rows(const double* pts, const double* labels, const int64_t* offsets, int B,
+                                                  int nx, int ny, int nz, int regular, const double* keep_labels_host,
+                                                  int n_keep, double* partial_ws, double* bbox, double* desc,
+                                                  uint32_t* bits_ws, void* occ, void* gt_occ, int out_dtype, int32_t* flags,
+                                                  int32_t* dropped, int32_t* counts_ws, int32_t* towers_ws,
+                                                  const float* params, const int32_t* kinds, int G, int kz, int kx, int ky,
+                                                  float* bank, int32_t* status, float* lambdas, const int32_t* order,
+                                                  int last, float* lambdas_out, void* prep, sn_stream_t stream,
+                                                  uint32_t* row_bits) {
+    return occupancy_fused_bank_impl(pts, labels, offsets, B, nx, ny, nz, regular, keep_labels_host, n_keep, partial_ws, bbox,
+                                     desc, bits_ws, occ, gt_occ, out_dtype, flags, dropped, counts_ws, towers_ws, params, kinds,
+                                     G, kz, kx, ky, bank, status, lambdas, order, last, lambdas_out, prep, stream, row_bits);
 }
 
 static int occupancy_sized_impl(const char* who, const double* pts, const double* labels, const int64_t* offsets, int B,

@@ -78,6 +78,7 @@ class VoxelGrids:
     dims: Optional[torch.Tensor] = None   # [B,3] i32 (n_x, n_y, n_z) per tile -- voxel-size mode: grids are padded to the maximum
     status: Optional[torch.Tensor] = None  # [B] i32, voxel-size mode: 1 = the tile needs more voxels than the maximum
     rider_done: bool = False               # the bank rider handed to voxelize_batch ran with the first launch
+    row_bits: Optional[torch.Tensor] = None  # [B,nz,ceil(nx/32)] i32, n-mode occupancy path: which (z, x) rows of occ hold a voxel
 
 
 def _labels_list(tower_label) -> List[float]:
@@ -137,8 +138,9 @@ def voxelize_batch(batch: PointBatch, voxelgrid_dims: Sequence[int] = (64, 64, 6
         occ, gt_occ, flags, dropped, desc, _ = _hip.voxel_occupancy_fused(
             batch.pts, batch.labels if want_t else None, batch.offsets, (nx, ny, nz), True,
             _labels_list(keep_labels) if want_t else (), want_gt_occ=want_gt_occ, out_dtype=occ_dtype,
-            bank_rider=bank_rider)
+            bank_rider=bank_rider, want_rows=max(nx, ny, nz) <= 64)   # (the grids whose bits the contraction can use)
         grids = VoxelGrids(None, None, None, None, occ, gt_occ, desc, dropped, flags)
+        grids.row_bits = _hip.rows_for(occ)
         grids.rider_done = bank_rider is not None
         return grids
     if bounds is None:

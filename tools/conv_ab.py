@@ -5,7 +5,10 @@ rounds in ONE process on the bench's C2 batch (cdna_hip_programming.md rule 24).
     python tools/conv_ab.py --skip      the z-walk with and without its empty-window skip (sn_set_option "conv_i8z_dense"),
                                         a dense / skip pair of rows on the C2 batch, on random 50 % occupancy (no window is
                                         empty: the price of the check) and on an all-zero batch (the floor of a launch that
-                                        skips every round), with the rounds run / skipped of one launch"""
+                                        skips every round), with the rounds run / skipped of one launch
+    python tools/conv_ab.py --skip --bits   the same three inputs through sn_conv_bank_prepared_rows: without row bits (the
+                                        static two-segment deal and its byte check), with bits and two segments, with bits
+                                        and four (the default with bits at Z = 64): the balanced deal, conv_i8z.inc"""
 import argparse
 import os
 import sys
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--points", type=int, default=100_000)
     ap.add_argument("--random-occ", type=float, default=0.0, help="random occupancy of this density instead of tiles")
     ap.add_argument("--skip", action="store_true", help="dense / skip rows of the z-walk on three inputs")
+    ap.add_argument("--bits", action="store_true", help="with --skip: hand the occupancy's row bits to the walk")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     specs, names, lambdas, last = synthetic_bank_spec()
@@ -45,6 +49,8 @@ def main():
                                  occ_dtype=torch.bool).occ
 
     prep = _hip.conv_bank_prep(bank)
+    if args.skip and args.bits:
+        return bits_ab(args, occ, bank, lam, prep)
     if args.skip:
         return skip_ab(args, occ, bank, lam, prep)
     use_prep = [False]
@@ -149,6 +155,56 @@ def skip_ab(args, tiles_occ, bank, lam, prep):
         print(f"{name:12s} {'dense' if dense else 'skip ':5s} median {float(np.median(ts)) * 1e3:8.1f} us  min {float(np.min(ts)) * 1e3:8.1f} us  "
               f"rounds run {ran} skipped {skipped} ({100.0 * ran / max(1, ran + skipped):5.1f} % run)  same bits {same}  "
               f"rounds {[round(t * 1e3, 1) for t in ts]}")
+    print(f"spin give-ups {_hip.conv_i8_spin_timeouts()}, device status {_hip.device_status()[0]}")
+
+
+def bits_ab(args, tiles_occ, bank, lam, prep):
+    """the prepared, served z-walk without row bits, with bits and two segments, with bits and four, interleaved"""
+    g = torch.Generator(device=tiles_occ.device).manual_seed(1)
+    inputs = {"C2 batch": tiles_occ,
+              "random 50 %": torch.rand(tiles_occ.shape, device=tiles_occ.device, generator=g) < 0.5,
+              "all zero": torch.zeros_like(tiles_occ)}
+    bits = {name: _hip.row_bits_of(x) for name, x in inputs.items()}
+    out = torch.empty(tiles_occ.shape, dtype=torch.float32, device=tiles_occ.device)
+    fn = _hip.load().sn_conv_bank_prepared_rows
+    B, _, Z, X, Y = tiles_occ.shape
+    G = bank.shape[0]
+    stream = torch.cuda.current_stream().cuda_stream
+    modes = {"no bits": (False, 0), "bits, 2 segments": (True, 2), "bits, 4 segments": (True, 4)}
+
+    def run(name, mode, n):
+        with_bits, seg = modes[mode]
+        _hip.set_option("conv_i8z_segments", seg)
+        for _ in range(n):
+            rc = fn(inputs[name].data_ptr(), _hip.SN_OCC8, bank.data_ptr(), lam.data_ptr(), prep.data_ptr(), B, Z, X, Y, G, 9, 9,
+                    9, None, out.data_ptr(), _hip.SN_F32, stream, 1, bits[name].data_ptr() if with_bits else None, None)
+            assert rc == 0, rc
+
+    rows = [(name, mode) for name in inputs for mode in modes]
+    res = {r: [] for r in rows}
+    kept = {}
+    t_spin = time.perf_counter()
+    while time.perf_counter() - t_spin < 0.3:
+        run("C2 batch", "no bits", 10)
+        torch.cuda.synchronize()
+    for r in range(args.rounds):
+        for name, mode in rows:
+            run(name, mode, 5)
+            torch.cuda.synchronize()
+            if r == 0:
+                kept[(name, mode)] = out.clone()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(name, mode, args.iters)
+            e1.record()
+            torch.cuda.synchronize()
+            res[(name, mode)].append(e0.elapsed_time(e1) / args.iters)
+    _hip.set_option("conv_i8z_segments", 0)
+    for name, mode in rows:
+        ts = res[(name, mode)]
+        same = torch.equal(kept[(name, mode)].view(torch.int32), kept[(name, "no bits")].view(torch.int32))
+        print(f"{name:12s} {mode:17s} median {float(np.median(ts)) * 1e3:8.1f} us  min {float(np.min(ts)) * 1e3:8.1f} us  "
+              f"same bits {same}  rounds {[round(t * 1e3, 1) for t in ts]}")
     print(f"spin give-ups {_hip.conv_i8_spin_timeouts()}, device status {_hip.device_status()[0]}")
 
 
