@@ -39,8 +39,10 @@ FLAGS_knn := -ffp-contract=off
 FLAGS_shape := -ffp-contract=off
 # render.hip: a projected coordinate is ((a0*x + a1*y) + a2*z) + a3 with every product and sum rounded once, as numpy rounds them
 FLAGS_render := -ffp-contract=off
+# voxel_pool.hip: bins with K1's fp64 rounding sequence (binning.h); a quantum is rint(fl(p - lo) * inv) and a mean lo + (S / n) * step, every fp64 operation rounded once
+FLAGS_voxel_pool := -ffp-contract=off
 
-SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn shape render
+SOURCES := cabi bank voxel conv conv_i8 conv_i8s conv_lin backward corr loss metrics ingest towers crops dbscan tower_score las kitti las_write voxel_cloud thin voxel_classes scan_merge quantile knn shape render voxel_pool
 OBJS    := $(SOURCES:%=$(OBJDIR)/%.o)
 
 all: $(OUT)/libscenenet_hip.so

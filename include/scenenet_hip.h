@@ -1795,6 +1795,79 @@ int sn_render_resolve(const uint64_t* keys, int K, int H, int W, const int64_t* 
                       uint32_t* depth_q, sn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------- *
+ * K24 -- voxel pooling: per voxel the mean, minimum or maximum of a coordinate or of a per-point value column, in up to
+ *        eight planes, and the count of the rows that took part.
+ * replaces: Vox.centroid_hist_on_voxel / Vox.centroid_reg_on_voxel, which core/datasets/torch_transforms.py:161-162 calls and
+ *           the reference's tree does not contain (build-defined: the mean position of each voxel's points next to the
+ *           density and the ratio); and the torch formulation (searchsorted for the flat indices, index_add_ /
+ *           scatter_reduce through floating-point atomics, whose sums depend on the order of arrival).
+ *
+ * batch:    the ragged CSR layout of K1, K17 and K18: pts [total,3] f64, offsets [B+1] i64 with offsets[0] = 0 and
+ *           offsets[B] <= total; rows at or beyond offsets[B] are not read.  Empty tiles are legal.
+ *           values [total,C] f64 row-major, 0 <= C <= SN_POOL_MAX_COLUMNS; nullable when no plane reads a column.
+ * planes:   1 <= P <= SN_POOL_MAX_PLANES.  Plane p reads source plane_source_host[p] (0, 1, 2: x, y, z; 3 + c: value column
+ *           c) and reduces with plane_op_host[p] (SN_POOL_MEAN / SN_POOL_MIN / SN_POOL_MAX).  A source may appear in several
+ *           planes.  Both lists are HOST arrays read by the call.
+ * rows:     a row is binned by K1's rule, bit for bit (the same device function as sn_voxel_scatter, sn_thin_count and
+ *           sn_voxel_classes), with desc [B, SN_DESC_LEN(nx, ny, nz)] as sn_voxel_prepare and its siblings build it.
+ *             a row with a NaN coordinate or outside the table on ANY axis      counted in unbinned [B] and nowhere else
+ *             a binned row with a NaN in a value column that SOME plane reads   counted in nan_rows [B] and nowhere else
+ *             every other row                                                   counts 1 in counts [B,nz,nx,ny] i32 and
+ *                                                                               takes part in EVERY plane
+ *           counts[b].sum() + unbinned[b] + nan_rows[b] == the tile's rows; with no plane on a value column counts equals
+ *           sn_voxel_scatter's counts bit for bit.  A size-mode descriptor is accepted with the caveat of sn_thin_count and
+ *           sn_voxel_classes: the padded table is used as it stands, so a foreign row above a tile's own last edge lands in
+ *           the padding cell n_a and is NOT counted in unbinned.
+ * MEAN:     a fixed-point mean, so that the bits depend neither on scheduling nor on the order of the rows.  For a
+ *           coordinate source a: lo = desc[b][a], hi = desc[b][3 + a]; for a value source c: lo, hi =
+ *           value_range_host[c][0], [1] (HOST, [C,2]; finite with hi > lo for every column a MEAN plane reads; nullable
+ *           when none does).  span = fl(hi - lo); inv = fl(4294967296.0 / span) if span > 0 and the quotient is finite,
+ *           else 0 (a one-point tile has hi == lo: its centroid is lo).  Per row t = fl(fl(p - lo) * inv); t = t > 0 ? t : 0
+ *           (so a NaN product -- an infinite difference times inv = 0 -- is 0); t = t < 2^32 ? t : 2^32; q = (int64)
+ *           rint(t).  -inf, -1e300 and every foreign row K1 clips into bin 0 so count as lo, +-inf values as the ends of
+ *           their range.  S = the sum of the q by 64-bit integer atomic add; the plane holds fl(lo + fl(fl((double)S /
+ *           (double)n) * step)), step = fl(span / 4294967296.0), n the voxel's count, every operation rounded once
+ *           (-ffp-contract=off).  Within span * 2^-33 of the fp64 mean of the clamped inputs (half a quantum per row).
+ * MIN/MAX:  by value, through the order-preserving 64-bit key of K18 and integer atomic min / max, the plane the winner's
+ *           64-bit pattern.  +-inf and denormals are ordinary values; of -0.0 and +0.0 in one voxel MAX gives +0.0 and MIN
+ *           -0.0.  (NaN cannot arrive: such a row is in nan_rows.)
+ * empty:    a voxel with counts == 0 holds `fill` in every plane, its bit pattern as given.
+ * out:      [B, P, nz, nx, ny] f64.
+ * ------------------------------------------------------------------------- */
+#define SN_POOL_MEAN 0
+#define SN_POOL_MIN 1
+#define SN_POOL_MAX 2
+#define SN_POOL_MAX_PLANES 8
+#define SN_POOL_MAX_COLUMNS 5
+#define SN_VOXEL_POOL_NO_LOOK 1
+
+/* Rows per workgroup of sn_voxel_pool (1024): host only -- lets a test put its sizes on the seams. */
+int sn_voxel_pool_chunk_points(void);
+/* Workspace bytes of sn_voxel_pool: 0 for every shape -- the call accumulates in `out` and `counts` themselves, and its `ws`
+ * is ignored (null is fine).  Kept in the interface so that a caller sizes a workspace by asking, not by knowing. */
+int64_t sn_voxel_pool_ws_bytes(int B, int nx, int ny, int nz, int P);
+
+/* Three launches on `stream` and no memset node: clear (the accumulators to what each reduction starts from, unbinned and
+ * nan_rows to 0), rows (per row that takes part one integer atomic add for the count and one 64-bit integer atomic per
+ * plane; a min / max atomic is sent only where a plain load of the cell shows that it can still change the cell --
+ * flags = SN_VOXEL_POOL_NO_LOOK sends it always: same result, for timing), decode.  Integer sums, minima and maxima: the
+ * result does not depend on scheduling.  No allocation, no synchronisation: capturable.
+ * The accumulators live in `out` and `counts` themselves (a row's P + 1 atomics go to P + 1 lines 8 * V bytes apart) and
+ * decode rewrites `out` in place.  [measured] a workspace of P + 1 consecutive words per voxel was 1.07 - 1.13 times slower
+ * on 32 tiles of 10^5 points at 64^3 and was taken out.
+ * SN_ERR_INVALID_ARG: a null pts / offsets / desc / out / counts / unbinned / nan_rows / plane list, values null with a plane
+ * that reads a column, C or P out of range, a source >= 3 + C, an unknown op, unknown flags, a MEAN plane on a column whose
+ * range is missing, not finite or without hi > lo, total <= 0, B <= 0, an extent <= 0, a pointer that is not 8-byte aligned
+ * (counts: 4-byte);  SN_ERR_UNSUPPORTED: total >=
+ * 2^31 (so that a count fits int32 and a sum int64), B > 65536, nx * ny * nz >= 2^31, edge tables (nx + ny + nz + 3
+ * doubles) beyond 64 KiB of LDS.  All checked before any launch; each leaves its message in sn_last_error(). */
+int sn_voxel_pool(const double* pts, const double* values, int C, const int64_t* offsets, int64_t total, int B,
+                  const double* desc, int nx, int ny, int nz, const int32_t* plane_source_host, const int32_t* plane_op_host,
+                  int P, const double* value_range_host, double fill, int flags, void* ws, double* out,
+                  int32_t* counts, int64_t* unbinned, int64_t* nan_rows, sn_stream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from ._hip import HipLibraryError, LIB_PATH
 from .geneos import (GENEO_kernel_torch, arrow, cone_kernel, cylinder_kernel, cylinderv2, neg_sphere_kernel,
                      negSpherev2)
 from .scene_net import GENEO_Layer, SCENE_Net, SCENE_Net_Class, SCENENetQuantile, SceneNet
-from .transforms import ToFullDense, ToTensor, Voxelization
+from .transforms import ToFullDense, ToTensor, Voxelization, xyz_ToFullDense, xyz_Voxelization
 from .voxelization import (PointBatch, VoxelGrids, hist_on_voxel, prob_to_label, reg_on_voxel, voxelize_batch,
                            vxg_to_xyz)
 from .pipeline import CapturedPipeline, ScenePipeline, shard_range
@@ -42,6 +42,8 @@ from .neighbours import (PointNeighbours, avg_dist_points, k_distance_curve, knn
 from .shapes import PointShapes, estimate_normals, select_by_shape, shape_colors, shape_features
 from .render import (RenderedViews, default_class_table, ortho_camera, perspective_camera, png_bytes, render_points,
                      render_pred_vs_gt, render_scan, render_voxelgrid, write_png)
+from .voxel_pool import (VoxelPool, centroid_hist_on_voxel, centroid_reg_on_voxel, voxel_centroids, voxel_downsample,
+                         voxel_pool)
 from .criterions import (BinaryDiceLoss, BinaryDiceLoss_BCE, FocalLoss, FocalTverskyLoss, GENEO_Dice_BCE, GENEO_Dice_Loss,
                          GENEO_Loss, GENEO_Tversky_Loss, IoULoss, QuantileGENEOLoss, QuantileLoss, TverskyLoss, WeightedMSE)
 
@@ -64,6 +66,8 @@ __all__ = ["SceneNet", "SCENE_Net", "SCENENetQuantile", "SCENE_Net_Class", "cyli
            "avg_dist_points", "PointShapes", "shape_features", "estimate_normals", "select_by_shape", "shape_colors",
            "RenderedViews", "ortho_camera", "perspective_camera", "render_points", "render_scan", "render_voxelgrid",
            "render_pred_vs_gt", "png_bytes", "write_png", "default_class_table",
+           "VoxelPool", "voxel_pool", "voxel_centroids", "centroid_hist_on_voxel", "centroid_reg_on_voxel", "voxel_downsample",
+           "xyz_Voxelization", "xyz_ToFullDense",
            "read_kitti_scan", "kitti_scan_lists", "semKITTI", "build_pole_samples", "build_pole_radius_samples", "lut_array", "HipLibraryError", "LIB_PATH", "WeightedMSE", "GENEO_Loss",
            "GENEO_Tversky_Loss", "GENEO_Dice_Loss", "GENEO_Dice_BCE", "TverskyLoss", "FocalTverskyLoss", "BinaryDiceLoss",
            "BinaryDiceLoss_BCE", "QuantileLoss", "QuantileGENEOLoss", "FocalLoss", "IoULoss"]

@@ -173,6 +173,10 @@ SYMBOLS = {
     "sn_render_chunk_points": (c_int, []),
     "sn_render_splat": (c_int, [_P, _P, ctypes.c_int64, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sn_render_resolve": (c_int, [_P, _I, _I, _I, _P, _I, _P, _P, _I, ctypes.c_uint32, ctypes.c_double, _P, _P, _P, _P]),
+    "sn_voxel_pool_chunk_points": (c_int, []),
+    "sn_voxel_pool_ws_bytes": (ctypes.c_int64, [_I, _I, _I, _I, _I]),
+    "sn_voxel_pool": (c_int, [_P, _P, _I, _P, ctypes.c_int64, _I, _P, _I, _I, _I, _P, _P, _I, _P, ctypes.c_double, _I, _P, _P,
+                              _P, _P, _P, _P]),
 }
 SN_CONV_PREP_BYTES = 16384
 SN_LOSS_WMSE, SN_LOSS_FOCAL_TVERSKY, SN_LOSS_DICE, SN_LOSS_WBCE = 1, 2, 4, 8
@@ -198,6 +202,8 @@ SN_SHAPE_SWEEPS, SN_SHAPE_NFEAT, SN_SHAPE_LAUNCHES = 4, 6, 5
 SN_RENDER_MAX_VIEWS, SN_RENDER_MAX_SPLAT = 64, 9
 SN_RENDER_ACCUMULATE, SN_RENDER_NO_LOOK, SN_RENDER_LOOK_ALWAYS = 1, 2, 4
 SN_RENDER_RGB16, SN_RENDER_DEPTH = 0, 1
+SN_POOL_MEAN, SN_POOL_MIN, SN_POOL_MAX = 0, 1, 2
+SN_POOL_MAX_PLANES, SN_POOL_MAX_COLUMNS, SN_VOXEL_POOL_NO_LOOK = 8, 5, 1
 OCC_MAX_WORDS = 16 * 1024
 
 
@@ -2356,3 +2362,61 @@ def render_resolve(keys: torch.Tensor, size: Sequence[int], offsets: torch.Tenso
                                   _ptr(rgba, torch.uint8, "rgba"), _ptr(index, torch.int64, "index"),
                                   _ptr(depth_q, torch.int32, "depth_q"), _stream())
     _check(rc, "sn_render_resolve")
+
+
+# --------------------------------------------------------------------------- #
+def voxel_pool_chunk_points() -> int:
+    """sn_voxel_pool_chunk_points: rows per workgroup of the pooling kernel (host only)."""
+    return int(load().sn_voxel_pool_chunk_points())
+
+
+def voxel_pool_ws_bytes(B: int, n_xyz: Sequence[int], P: int) -> int:
+    """sn_voxel_pool_ws_bytes: workspace bytes of voxel_pool (host only): 0, the call accumulates in its outputs."""
+    nx, ny, nz = (int(v) for v in n_xyz)
+    return int(load().sn_voxel_pool_ws_bytes(int(B), nx, ny, nz, int(P)))
+
+
+@_on_tensor_device
+def voxel_pool(pts: torch.Tensor, values: Optional[torch.Tensor], offsets: torch.Tensor, desc: torch.Tensor,
+               n_xyz: Sequence[int], sources: Sequence[int], ops: Sequence[int],
+               value_ranges: Optional[Sequence[Sequence[float]]], fill: float, out: torch.Tensor, counts: torch.Tensor,
+               unbinned: torch.Tensor, nan_rows: torch.Tensor, look: bool = True) -> None:
+    """sn_voxel_pool: pts [total,3] f64, values [total,C] f64 | None, offsets [B+1] i64, desc [B, desc_len]; plane p reduces
+    source sources[p] (0, 1, 2: x, y, z; 3 + c: column c) with ops[p] (SN_POOL_MEAN / MIN / MAX); value_ranges [C] pairs (lo,
+    hi) on the host, read for the columns a MEAN plane reads -> out [B,P,nz,nx,ny] f64, counts [B,nz,nx,ny] i32, unbinned [B]
+    i64, nan_rows [B] i64, all caller-owned; the accumulators live in out and counts themselves.  look=False sends every min /
+    max atomic (same result; for timing).  No allocation, no synchronisation."""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise HipLibraryError(f"pts must be [total, 3] (got {tuple(pts.shape)})")
+    total, B = int(pts.shape[0]), int(offsets.numel()) - 1
+    nx, ny, nz = (int(v) for v in n_xyz)
+    P = len(sources)
+    if len(ops) != P:
+        raise HipLibraryError("sources and ops disagree in length")
+    C = 0
+    if values is not None:
+        if values.dim() != 2 or int(values.shape[0]) != total:
+            raise HipLibraryError(f"values must be [total, C] = [{total}, C] (got {tuple(values.shape)})")
+        C = int(values.shape[1])
+    if tuple(desc.shape) != (B, desc_len(nx, ny, nz)):
+        raise HipLibraryError(f"desc must be [B, desc_len(nx, ny, nz)] = [{B}, {desc_len(nx, ny, nz)}] "
+                              f"(got {tuple(desc.shape)})")
+    V = nx * ny * nz
+    if out.numel() != B * P * V or counts.numel() != B * V or unbinned.numel() != B or nan_rows.numel() != B:
+        raise HipLibraryError("out must hold B * P * nz * nx * ny cells, counts B * nz * nx * ny, unbinned and nan_rows B")
+    src = (ctypes.c_int32 * max(P, 1))(*[int(v) for v in sources])
+    op = (ctypes.c_int32 * max(P, 1))(*[int(v) for v in ops])
+    rng = None
+    if value_ranges is not None:
+        flat = [float(v) for pair in value_ranges for v in pair]
+        if len(flat) != 2 * C:
+            raise HipLibraryError(f"value_ranges must hold C = {C} pairs (lo, hi)")
+        rng = (ctypes.c_double * max(len(flat), 1))(*flat)
+    rc = load().sn_voxel_pool(_ptr(pts, torch.float64, "pts"), _ptr(values, torch.float64, "values"), C,
+                              _ptr(offsets, torch.int64, "offsets"), total, B, _ptr(desc, torch.float64, "desc"), nx, ny, nz,
+                              ctypes.cast(src, c_void_p), ctypes.cast(op, c_void_p), P,
+                              None if rng is None else ctypes.cast(rng, c_void_p), float(fill),
+                              0 if look else SN_VOXEL_POOL_NO_LOOK, None, _ptr(out, torch.float64, "out"),
+                              _ptr(counts, torch.int32, "counts"), _ptr(unbinned, torch.int64, "unbinned"),
+                              _ptr(nan_rows, torch.int64, "nan_rows"), _stream())
+    _check(rc, "sn_voxel_pool")

@@ -1,5 +1,5 @@
 """Host-side mirror of core/datasets/torch_transforms.py: `ToTensor` (:9-13), `ToFullDense` (:17-40),
-`Voxelization` (:44-81) -- same names, constructor arguments and call signatures, so
+`Voxelization` (:44-81), `xyz_ToFullDense` (:109-124), `xyz_Voxelization` (:127-166) -- same names, constructor arguments and call signatures, so
 `Compose([Voxelization(...), ToTensor(), ToFullDense(apply=(True, True))])` (scripts/main.py:138-140)
 works unchanged.  `Voxelization` runs the HIP voxeliser (one bbox + one scatter pass produce both the
 density and the ground-truth grid; the reference voxelises the same points twice).
@@ -76,3 +76,34 @@ class Voxelization:
                                  want_density=True, want_gt=True, want_occ=False)
         # vox-point-density, vox-tower-prob : [1, nz, nx, ny] float64 numpy, like the reference
         return g.density[0].cpu().numpy(), g.gt[0].cpu().numpy()
+
+
+# ---- centroid versions
+class xyz_ToFullDense:
+    """torch_transforms.py:109-124: the centroid grid as it is, the density and the tower ratio made binary."""
+
+    def __call__(self, sample):
+        xyz, dense, labels = sample
+        return xyz, (dense > 0).to(dense), (labels > 0).to(labels)
+
+
+class xyz_Voxelization:
+    """torch_transforms.py:127-166.  The reference calls Vox.centroid_hist_on_voxel and Vox.centroid_reg_on_voxel, which its
+    tree does not contain; here they are scene_net_amd.voxel_pool's (the mean position of each voxel's points, 0 where the
+    voxel is empty).  One voxelisation gives the density and the ratio and one pooling call the centroids, all binned by the
+    same table, so the equality the reference asserts between the two calls' centroid channels holds by construction."""
+
+    def __init__(self, keep_labels, vox_size: Tuple[int] = None, vxg_size: Tuple[int] = None) -> None:
+        if vox_size is None and vxg_size is None:
+            ValueError("Voxel size or Voxelgrid size must be provided")  # constructed, never raised (reference :148-149)
+        self.vox_size = vox_size
+        self.vxg_size = vxg_size
+        self.label = keep_labels
+
+    def __call__(self, sample):
+        from .voxel_pool import _centroids_next_to
+        pts, labels = sample
+        _check_worker_context()
+        cen, g = _centroids_next_to(pts, labels, self.label, self.vxg_size, self.vox_size, True, True)
+        # xyz-vox-centroid [1,3,nz,nx,ny], vox-point-density [1,nz,nx,ny], vox-tower-prob [1,nz,nx,ny]: float64 numpy
+        return cen[None].cpu().numpy(), g.density[0].cpu().numpy(), g.gt[0].cpu().numpy()
