@@ -322,6 +322,28 @@ int sn_conv_fused_prepared(const void* x, int x_dtype, const float* bank, const 
  * the halo within 160 KiB of LDS), else 0: the caller's dispatch predicate, from the same plan the launch uses. */
 int sn_conv_fused_supported(int B, int Z, int X, int Y, int kz, int kx, int ky);
 
+/* What sn_conv_fused (and its _v / _prepared forms) would launch for these arguments under the options in force now: host
+ * arithmetic only, no launch, no device memory; works without a device (256 compute units are then counted).  The shape
+ * plan is the launch's own (the one sn_conv_fused_supported answers from), and the grid size and the deferral rule come
+ * from the helper the launch and the kernel themselves call, so the query cannot drift from them.  The kernel is
+ * persistent: workgroup w walks tiles w, w + [5], w + 2 [5], ...; the next tile's halo is requested into registers while the
+ * current tile's MFMAs run, and with a deferred epilogue a tile's outputs are activated and stored between the MFMAs of the
+ * workgroup's NEXT tile -- both only from a workgroup's second tile on, i.e. where [4] > [5].  plan8 (8 x int32, host memory):
+ *   [0] 1: kernel rows packed at 24 bytes of K (ky <= 9 and option "conv_lin_no24" = 0), 0: at 32 bytes
+ *   [1] MFMA steps per tile: ceil(3 kz kx / 8) at 24 bytes, ceil(kz kx / 2) at 32
+ *   [2] 1: deferred epilogue ([1] >= 16), 0: every tile is finished at once
+ *   [3] halo passes per tile, ceil(halo rows / 25) with (8 + kz - 1)(16 + kx - 1) halo rows: the first 16 passes travel
+ *       through registers, more than 16 means the synchronous remainder pass runs
+ *   [4] workgroup tiles (8 x 16 x 64): B * ceil(Z / 8) * ceil(X / 16) * ceil(Y / 64)
+ *   [5] workgroups launched: min([7], [4])
+ *   [6] dynamic LDS of the launch, bytes
+ *   [7] compute units counted
+ * G enters the kernel's prologue only (any G > 0 gives the same plan).  Returns SN_OK, SN_ERR_INVALID_ARG (null plan8, an
+ * extent <= 0) or SN_ERR_UNSUPPORTED where sn_conv_fused returns it (Y % 4 != 0, ky window, LDS).  No reference counterpart
+ * (F.conv3d has no tile walk to ask about): this is what lets tests/test_gpu_conv_lin_walk.py size a batch so that every
+ * workgroup walks several tiles on the device at hand, and name the fork of the kernel a case ran. */
+int sn_conv_fused_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8);
+
 /* SceneNet.forward for FLOAT grids that are usually binary occupancy -- what the reference itself feeds: f64 {0., 1.}
  * out of ToFullDense (core/datasets/torch_transforms.py:33-34).  One pass writes (x != 0) into occ_ws [B*Z*X*Y] bytes
  * and raises not_binary[0] when an element is neither 0 nor 1; then the int8 form (sn_conv_fused on the bytes, or

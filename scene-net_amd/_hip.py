@@ -52,6 +52,7 @@ SYMBOLS = {
     "sn_launch_timing_events": (c_int, [_P, _P]),
     "sn_conv_fused": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sn_conv_fused_supported": (c_int, [_I, _I, _I, _I, _I, _I, _I]),
+    "sn_conv_fused_plan": (c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sn_forward_auto": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "sn_voxel_bbox": (c_int, [_P, _P, _I, _P, _P]),
     "sn_voxel_desc": (c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
@@ -669,6 +670,39 @@ def conv_fused_supported(x: torch.Tensor, kernel_size: Sequence[int]) -> bool:
     kz, kx, ky = (int(k) for k in kernel_size)
     B, _, Z, X, Y = x.shape
     return bool(load().sn_conv_fused_supported(int(B), int(Z), int(X), int(Y), kz, kx, ky))
+
+
+class ConvFusedPlan(NamedTuple):
+    """sn_conv_fused_plan's eight words (include/scenenet_hip.h)."""
+    w24: bool            # kernel rows packed at 24 bytes of K (else 32)
+    nsteps: int          # MFMA steps per tile
+    deferred: bool       # a tile's outputs are finished between the MFMAs of the workgroup's next tile
+    halo_passes: int     # > 16: the synchronous remainder pass runs
+    ntiles: int
+    workgroups: int
+    lds_bytes: int
+    cus: int
+
+    @property
+    def tiles_per_workgroup_min(self) -> int:
+        return self.ntiles // self.workgroups
+
+    @property
+    def tiles_per_workgroup_max(self) -> int:
+        return -(-self.ntiles // self.workgroups)
+
+
+def conv_fused_plan(x_or_shape, kernel_size: Sequence[int], G: int = 1) -> ConvFusedPlan:
+    """What conv_fused(x, bank, lambdas) would launch under the options in force (sn_conv_fused_plan: host only, no launch,
+    no device needed).  x_or_shape: a [B,1,Z,X,Y] tensor on any device, or that shape; kernel_size: (kz, kx, ky)."""
+    shape = tuple(x_or_shape.shape) if isinstance(x_or_shape, torch.Tensor) else tuple(x_or_shape)
+    if len(shape) != 5 or shape[1] != 1:
+        raise HipLibraryError(f"x must be [B,1,Z,X,Y] (got {shape})")
+    B, _, Z, X, Y = (int(v) for v in shape)
+    kz, kx, ky = (int(k) for k in kernel_size)
+    p = (ctypes.c_int32 * 8)()
+    _check(load().sn_conv_fused_plan(B, Z, X, Y, int(G), kz, kx, ky, ctypes.cast(p, c_void_p)), "sn_conv_fused_plan")
+    return ConvFusedPlan(bool(p[0]), int(p[1]), bool(p[2]), int(p[3]), int(p[4]), int(p[5]), int(p[6]), int(p[7]))
 
 
 @_on_tensor_device

@@ -248,7 +248,7 @@ extern "C" int sn_device_status_clear(void) {
     return SN_OK;
 }
 
-extern "C" int sn_version(void) { return 106; }   // 106: row bits (sn_voxel_occupancy_fused_rows, _fused_bank_rows, sn_conv_bank_prepared_rows); 105: sn_conv_corr_plan; 104: sn_voxel_onepass_giveups; 103: round 4 (sticky device status, sn_launch_timing_events); 102: round-3 entries (riders, sn_conv_corr_ws, sn_conv_fused_v, sn_loss_*_m / _u)
+extern "C" int sn_version(void) { return 107; }   // 107: sn_conv_fused_plan; 106: row bits (sn_voxel_occupancy_fused_rows, _fused_bank_rows, sn_conv_bank_prepared_rows); 105: sn_conv_corr_plan; 104: sn_voxel_onepass_giveups; 103: round 4 (sticky device status, sn_launch_timing_events); 102: round-3 entries (riders, sn_conv_corr_ws, sn_conv_fused_v, sn_loss_*_m / _u)
 
 extern "C" const char* sn_last_error(void) { return sn::error_buffer(); }
 

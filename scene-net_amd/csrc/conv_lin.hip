@@ -97,7 +97,8 @@ __global__ __launch_bounds__(kThreads) void conv_lin_i8_kernel(const uint8_t* __
     // Thread -> (dword column i, first halo row): kThreads / DW = 25 rows per pass (the last 12 threads idle), so a
     // pass advances every thread by the same (dz, dx) and the row split r -> (zz, xx) is incremental -- one add and
     // one wrap per load instead of divisions (every thread runs this 16 times per tile, next to the MFMA loop).
-    constexpr int RPP = kThreads / DW;
+    constexpr int RPP = kLinRowsPerPass;
+    static_assert(RPP == kThreads / DW, "a pass is one dword per thread");
     const int h_i = tid % DW, h_r0 = tid / DW;
     const bool h_thread = tid < RPP * DW;
     const int h_zz0 = h_r0 / s.XP, h_xx0 = h_r0 - h_zz0 * s.XP;
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void conv_lin_i8_kernel(const uint8_t* __
     // Deferred epilogue: a tile's 16 outputs per lane stay in registers as pre-activations and are finished
     // (exp / rcp / 16-byte stores) BETWEEN the MFMAs of the next tile's first 16 steps, instead of in a phase where
     // the matrix pipe idles.  Needs >= 16 steps; smaller kernels finish each tile at once.
-    const bool defer = s.nsteps >= 16 && !SN_DBG(s, 16);
+    const bool defer = lin_defers(s.nsteps) && !SN_DBG(s, 16);
     float pv[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) pv[k] = 0.f;
@@ -497,6 +498,29 @@ extern "C" int sn_conv_fused_supported(int B, int Z, int X, int Y, int kz, int k
     return lin_plan(B, Z, X, Y, 1, kz, kx, ky, s, lds, w24) ? 1 : 0;
 }
 
+// What conv_fused_lin would launch: lin_plan's shape, lin_grid's workgroups, lin_defers' epilogue -- the launch's own three.
+// Host only.
+extern "C" int sn_conv_fused_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, int32_t* plan8) {
+    if (!plan8) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_fused_plan: null plan8");
+    if (B <= 0 || Z <= 0 || X <= 0 || Y <= 0 || G <= 0 || kz <= 0 || kx <= 0 || ky <= 0)
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_fused_plan: non-positive extent");
+    LinShape s;
+    size_t lds = 0;
+    bool w24 = false;
+    if (!lin_plan(B, Z, X, Y, G, kz, kx, ky, s, lds, w24))
+        return sn::fail(SN_ERR_UNSUPPORTED, "sn_conv_fused_plan: shape outside the kernel (Y %% 4, ky window, LDS)");
+    const int cus = num_cus();
+    plan8[0] = w24 ? 1 : 0;
+    plan8[1] = s.nsteps;
+    plan8[2] = lin_defers(s.nsteps) ? 1 : 0;
+    plan8[3] = (s.rows + kLinRowsPerPass - 1) / kLinRowsPerPass;
+    plan8[4] = s.ntiles;
+    plan8[5] = lin_grid(s.ntiles, cus);
+    plan8[6] = (int)lds;
+    plan8[7] = cus;
+    return SN_OK;
+}
+
 // returns SN_ERR_UNSUPPORTED (without touching the error text) when the shape is outside this kernel
 int sn::conv_fused_lin(const uint8_t* x, const float* bank, const float* lambdas, int B, int Z, int X, int Y, int G,
                        int kz, int kx, int ky, void* out, int out_dtype, hipStream_t stream, int32_t* verdict,
@@ -507,8 +531,7 @@ int sn::conv_fused_lin(const uint8_t* x, const float* bank, const float* lambdas
     bool w24 = false;
     if (!lin_plan(B, Z, X, Y, G, kz, kx, ky, s, lds, w24)) return SN_ERR_UNSUPPORTED;
     s.gate = sn::current_gate();
-    int grid = num_cus();
-    if (grid > s.ntiles) grid = s.ntiles;
+    const int grid = lin_grid(s.ntiles, num_cus());
     s.dbg = sn::debug_env_int("SN_CONV_LIN_DBG");   // (0 in the product: common.h)
     s.tol = sn::conv_i8_tolerance();
     if (out_dtype == SN_BF16) s.tol = 0.0f;   // bf16 storage rounds at 2^-9: the 24-bit fixed point is not what limits it

@@ -9,6 +9,7 @@ constexpr int kLinYB = 80;                  // halo bytes per row (64 + 16) = 5 
 // The halo is stored CHUNK-MAJOR, [chunk c][row r] x 16 bytes with the rows padded to a multiple of 16: the 16 lanes
 // one ds_read_b128 cycle serves (8 with a window's first chunk, 8 with its second) then fall on 16 distinct 16-byte
 // bank groups.
+constexpr int kLinRowsPerPass = kLinThreads / (kLinYB / 4);   // halo rows one pass of the workgroup loads: a dword per thread
 constexpr int kLinMaxLds = 160 * 1024;
 
 struct LinShape {
@@ -216,6 +217,13 @@ __device__ __forceinline__ bool lin_tables(const float* __restrict__ bank, const
     if (tid == 0) *scale_dst = misc[0];
     return false;
 }
+
+// The walk's two decisions outside the shape plan, each taken in ONE place: the kernel and the plan query
+// (sn_conv_fused_plan) ask lin_defers, the launch and the query ask lin_grid.
+// lin_defers: a tile's outputs ride along the first 16 MFMA steps of the workgroup's next tile -- needs that many steps.
+__host__ __device__ inline bool lin_defers(int nsteps) { return nsteps >= 16; }
+// lin_grid: persistent, one workgroup per compute unit (the LDS admits one), never more workgroups than tiles.
+inline int lin_grid(int ntiles, int cus) { return cus < ntiles ? cus : ntiles; }
 
 inline bool lin_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky, LinShape& s, size_t& lds, bool& w24) {
     if (B <= 0 || Z <= 0 || X <= 0 || Y <= 0 || kz <= 0 || kx <= 0 || ky <= 0 || Y % 4 != 0) return false;

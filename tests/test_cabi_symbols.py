@@ -24,7 +24,7 @@ def test_header_symbols_are_bound_and_exported():
     declared = _declared_symbols()
     assert {"sn_geneo_bank", "sn_conv_bank", "sn_voxel_bbox", "sn_voxel_desc", "sn_voxel_scatter",
             "sn_voxel_finalize", "sn_voxel_occupancy", "sn_voxel_prepare", "sn_last_error", "sn_version",
-            "sn_conv_corr_plan"} <= declared
+            "sn_conv_corr_plan", "sn_conv_fused_plan"} <= declared
     assert declared == set(_hip.SYMBOLS), "ctypes table and header disagree"
     lib = ctypes.CDLL(_hip.LIB_PATH)
     for name in declared:
@@ -79,6 +79,16 @@ def test_argument_checks_need_no_gpu():
     assert lib.sn_voxel_occupancy_plan(512, 512, 512, 1, 1, 0, 0, 1, 1, 1, 1, p) == -2
     assert b"LDS bitmap" in lib.sn_last_error()
     assert lib.sn_voxel_occupancy_plan(64, 64, 64, 2, 1, 1, 0, 1, 1, 1, 1, p) == 0
+    # the linear forward's plan query: host arithmetic, refused like the launch it describes
+    assert lib.sn_conv_fused_plan(1, 8, 16, 64, 16, 9, 9, 9, None) == -1
+    assert b"null" in lib.sn_last_error()
+    for bad in ((0, 8, 16, 64, 16, 9, 9, 9), (1, 8, -16, 64, 16, 9, 9, 9), (1, 8, 16, 64, 0, 9, 9, 9),
+                (1, 8, 16, 64, 16, 9, 0, 9)):
+        assert lib.sn_conv_fused_plan(*bad, p) == -1
+        assert b"non-positive" in lib.sn_last_error()
+    assert lib.sn_conv_fused_plan(1, 8, 16, 66, 16, 9, 9, 9, p) == -2      # Y % 4 != 0, where sn_conv_fused refuses
+    assert b"Y % 4" in lib.sn_last_error()
+    assert lib.sn_conv_fused_plan(1, 8, 16, 64, 16, 9, 9, 9, p) == 0
     assert lib.sn_grid_to_points(None, 0, 4, 4, 4, None, None, p, None) == -1
     assert lib.sn_grid_to_points(p, 0, 4, 0, 4, None, None, p, None) == -1   # empty grid
     assert b"empty" in lib.sn_last_error()
