@@ -349,7 +349,10 @@ int sn_conv_fused_plan(int B, int Z, int X, int Y, int G, int kz, int kx, int ky
  * and raises not_binary[0] when an element is neither 0 nor 1; then the int8 form (sn_conv_fused on the bytes, or
  * sn_conv_bank where that does not serve the shape) and the fp32 form (sn_conv_bank on x) of the same forward are
  * BOTH enqueued, each gated on that device flag: one runs, the other exits in its first instruction.  No host
- * synchronisation, same output contract as sn_conv_bank(out only).  x: SN_F32 | SN_F64, 16-byte aligned. */
+ * synchronisation, same output contract as sn_conv_bank(out only).  x: SN_F32 | SN_F64, 16-byte aligned; occ_ws 4-byte
+ * aligned; out: SN_F32 | SN_F64.  Every argument is checked before the first launch: SN_ERR_INVALID_ARG (a null pointer, an
+ * extent <= 0, another x_dtype or out_dtype, a misaligned x or occ_ws; sn_last_error() names the argument) and
+ * SN_ERR_UNSUPPORTED (a shape sn_conv_bank_plan refuses) leave occ_ws, not_binary and out untouched. */
 int sn_forward_auto(const void* x, int x_dtype, const float* bank, const float* lambdas, int B, int Z, int X, int Y,
                     int G, int kz, int kx, int ky, uint8_t* occ_ws, int32_t* not_binary, void* out, int out_dtype,
                     sn_stream_t stream);

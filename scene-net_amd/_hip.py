@@ -765,10 +765,17 @@ def conv_fused_prep_verdict(blob: torch.Tensor, kernel_size: Sequence[int]) -> t
 @_on_tensor_device
 def forward_auto(x: torch.Tensor, bank: torch.Tensor, lambdas: torch.Tensor, out_dtype: Optional[torch.dtype] = None):
     """sn_forward_auto: the forward output for a float grid; binary grids (the reference's f64 {0,1} input) take the
-    int8 path, anything else the fp32 contraction, decided on the device.  Returns (out, not_binary flag [1] i32)."""
+    int8 path, anything else the fp32 contraction, decided on the device.  Returns (out, not_binary flag [1] i32).
+    out_dtype: float32 | float64 (sn_conv_bank's output contract; default x's own)."""
+    if x.dim() != 5 or x.shape[1] != 1:
+        raise HipLibraryError(f"x must be [B,1,Z,X,Y] (got {tuple(x.shape)})")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise HipLibraryError(f"x dtype {x.dtype} unsupported (f32, f64; byte grids: conv_fused / conv_bank)")
     B, _, Z, X, Y = x.shape
     G, kz, kx, ky = bank.shape
     out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise HipLibraryError(f"out_dtype {out_dtype} unsupported (f32, f64)")
     if x.data_ptr() % 16:   # a sliced view (x[1:] of an odd-sized grid): the binary check reads 16-byte vectors
         x = x.clone()
     out = torch.empty((B, 1, Z, X, Y), dtype=out_dtype, device=x.device)

@@ -610,14 +610,27 @@ __global__ __launch_bounds__(256) void binarize_kernel(const T* __restrict__ x, 
 extern "C" int sn_forward_auto(const void* x, int x_dtype, const float* bank, const float* lambdas, int B, int Z, int X,
                                int Y, int G, int kz, int kx, int ky, uint8_t* occ_ws, int32_t* not_binary, void* out,
                                int out_dtype, sn_stream_t stream) {
-    if (!x || !bank || !lambdas || !occ_ws || !not_binary || !out)
-        return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: null pointer");
-    if (B <= 0 || Z <= 0 || X <= 0 || Y <= 0 || G <= 0 || kz <= 0 || kx <= 0 || ky <= 0)
-        return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: non-positive extent");
+    // everything either form could refuse is refused HERE: once binarize_kernel is enqueued the caller's occ_ws, flag and
+    // out are written, and an error after that would come back with those side effects
+    const struct { const void* p; const char* name; } ptrs[] = {{x, "x"}, {bank, "bank"}, {lambdas, "lambdas"},
+                                                               {occ_ws, "occ_ws"}, {not_binary, "not_binary"}, {out, "out"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: null pointer %s", a.name);
+    const struct { int v; const char* name; } extents[] = {{B, "B"}, {Z, "Z"}, {X, "X"}, {Y, "Y"},
+                                                          {G, "G"}, {kz, "kz"}, {kx, "kx"}, {ky, "ky"}};
+    for (const auto& e : extents)
+        if (e.v <= 0) return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: non-positive extent %s = %d", e.name, e.v);
     if (x_dtype != SN_F32 && x_dtype != SN_F64)
-        return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: x must be SN_F32 or SN_F64 (byte grids: sn_conv_fused)");
-    if ((uintptr_t)x % 16 || (uintptr_t)occ_ws % 4)
-        return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: x must be 16-byte, occ_ws 4-byte aligned");
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: x_dtype %d: x must be SN_F32 or SN_F64 (byte grids: "
+                                            "sn_conv_fused)", x_dtype);
+    if (out_dtype != SN_F32 && out_dtype != SN_F64)   // sn_conv_bank's contract: the fp32 form has no other store
+        return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: out_dtype %d: out must be SN_F32 or SN_F64", out_dtype);
+    if ((uintptr_t)x % 16) return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: x must be 16-byte aligned");
+    if ((uintptr_t)occ_ws % 4) return sn::fail(SN_ERR_INVALID_ARG, "sn_forward_auto: occ_ws must be 4-byte aligned");
+    {   // a shape the fp32 form does not take (ky window, LDS, grid size): every form ends there, so ask its planner (host only)
+        int32_t plan8[8];
+        if (int rc = sn_conv_bank_plan(x_dtype, B, Z, X, Y, G, kz, kx, ky, plan8)) return rc;
+    }
     hipStream_t s = sn::as_stream(stream);
     const size_t n = (size_t)B * Z * X * Y;
     if (hipMemsetAsync(not_binary, 0, sizeof(int32_t), s) != hipSuccess) return sn::check_launch("sn_forward_auto(memset)");
