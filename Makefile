@@ -55,11 +55,12 @@ $(OUT)/libscenenet_hip.so: $(OBJS)
 	@mkdir -p $(OUT)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(OBJS) -o $@
 
-asm:
+asm: $(SOURCES:%=build/asm/%.s)
+
+build/asm/%.s: $(SRC)/%.hip include/scenenet_hip.h $(wildcard $(SRC)/*.inc) $(wildcard $(SRC)/*.h)
 	@mkdir -p build/asm
-	for f in $(SOURCES); do \
-	  $(HIPCC) $(CXXFLAGS) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage \
-	    $(SRC)/$$f.hip -o build/asm/$$f.s 2> build/asm/$$f.usage.txt || exit 1; done
+	$(HIPCC) $(CXXFLAGS) $(FLAGS_$*) -S --cuda-device-only -Rpass-analysis=kernel-resource-usage $< -o $@ \
+	  2> build/asm/$*.usage.txt
 
 clean:
 	rm -rf build $(OUT)

@@ -29,6 +29,7 @@ import torch
 
 from . import _hip
 from ._hip import SN_CROP_BOX, HipLibraryError
+from .voxelization import _device_f64
 
 STAT_NAMES = ("n_points", "n_core", "first_core_index")
 DEFAULT_MAX_CELLS = 1 << 18
@@ -86,12 +87,6 @@ class PointClusters:
             raise IndexError(f"cluster {k} of {len(sizes) - 1}")
         at = sum(sizes[:k + 1])
         return src[at:at + sizes[k + 1]]
-
-
-def _device_f64(t, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise HipLibraryError(f"{name} must live on a HIP device; there is no CPU path")
-    return t.to(torch.float64).contiguous()
 
 
 def _keep_tensor(keep, dev) -> torch.Tensor:

@@ -29,7 +29,7 @@ import torch
 
 from . import _hip
 from ._hip import SN_CROP_BOX, HipLibraryError
-from .voxelization import PointBatch
+from .voxelization import PointBatch, _device_f64
 
 
 @dataclass
@@ -88,12 +88,6 @@ class ScanCrops:
         if self.src is None:
             raise HipLibraryError("the crops were made with want_src=False")
         return self.src[:int(self.offsets[-1])]
-
-
-def _device_f64(t, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise HipLibraryError(f"{name} must live on a HIP device; there is no CPU path")
-    return t.to(torch.float64).contiguous()
 
 
 def crop_regions(pts: torch.Tensor, regions: torch.Tensor, kinds: Optional[torch.Tensor] = None,

@@ -1,16 +1,22 @@
-// The cell grid of the neighbourhood kernels, shared by dbscan.hip (K10) and knn.hip (K21): cubic cells of side
-// k * eps * (1 + 2^-20), points binned by axis_cell (monotone, clamped), so that two points within eps of each other never
-// sit two cells apart and the 27 cells around a point's own hold every neighbour.  One rule, one proof, one text.
+// The cell grid of the neighbourhood kernels, shared by dbscan.hip (K10), knn.hip (K21) and shape.hip (K22): cubic cells of
+// side k * eps * (1 + 2^-20), points binned by axis_cell (monotone, clamped), so that two points within eps of each other
+// never sit two cells apart and the 27 cells around a point's own hold every neighbour.  One rule, one proof, one text.
 //
 // The grid is an accelerator only.  Points are counting-sorted into cell order as rows (x, y, z, position, cell): the
 // populations per cell (integer atomics, the files' own launch 1), their exclusive prefix and the cursors (cell_starts, one
 // workgroup), the rows stored where the cursors say (scatter_row).  With z the fastest cell axis the three cells of one
 // (x, y) column are ONE contiguous run of rows: 9 runs per home point (for_candidates).  The order of rows inside a cell depends
 // on scheduling (an integer cursor); every result is a count, a minimum, a set union or a function of the candidate SET
-// over the runs, so none does.  Device text and one host helper, no kernels: a trace keeps telling K10's launches from K21's.
+// over the runs, so none does.  K21 and K22 sort a packed batch tile by tile (the key is tile * cells + local cell): the
+// bodies of their zero, cells and scatter launches, the layout of the sort's arrays and the checks of the grid's arguments
+// are at the end of this file; K10 sorts selected positions without tiles, by kernels of its own.  Device text and host
+// helpers, no kernels: a trace keeps telling one call's launches from another's.
 #pragma once
+#include "common.h"
+#include "packed_rows.h"
 #include "scan.h"
 #include <hip/hip_runtime.h>
+#include <cmath>
 
 namespace {
 
@@ -101,6 +107,88 @@ __device__ __forceinline__ void for_candidates(const CellGrid& g, const int32_t*
             for (int j = a; j < b; ++j)
                 if (!f(rows[j])) return;
         }
+}
+
+// ---- the per-tile counting sort of a packed batch (K21, K22).  The __global__ kernels stay in knn.hip and shape.hip under
+// their own names, as wrappers of these bodies; each file keeps the stores of a row that no tile owns.
+// launch "zero": population c of `cells` (a kernel, not a memset node: DESIGN section 7 K21, "Launches")
+__device__ __forceinline__ void zero_population(int32_t* __restrict__ pop, int cells, int c) {
+    if (c < cells) pop[c] = 0;
+}
+
+// launch "cells", live row i: its key tile * g.cells + the cell of its point from the tile's own lo, stored and counted
+__device__ __forceinline__ void count_packed_row(const double* __restrict__ pts, const int64_t* __restrict__ offsets, int B,
+                                                 const double* __restrict__ lo, const CellGrid& g, int i,
+                                                 int32_t* __restrict__ cell_of, int32_t* __restrict__ pop) {
+    const int b = sn::tile_of_row(offsets, B, i);
+    CellGrid t = g;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t.lo[a] = lo[(size_t)b * 3 + a];
+    const int c = b * g.cells + cell_of_point(t, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2]);
+    cell_of[i] = c;
+    atomicAdd(pop + c, 1);
+}
+
+// launch "scatter", live row i of m: its Row into cell order
+__device__ __forceinline__ void scatter_packed_row(const double* __restrict__ pts, int i, int m,
+                                                   const int32_t* __restrict__ cell_of, int32_t* __restrict__ cursor,
+                                                   Row* __restrict__ rows) {
+    Row r;
+    r.x = pts[(size_t)i * 3];
+    r.y = pts[(size_t)i * 3 + 1];
+    r.z = pts[(size_t)i * 3 + 2];
+    r.pos = i;
+    r.cell = cell_of[i];
+    scatter_row(r, m, cursor, rows);
+}
+
+// ---- host.  The sort's four arrays in a workspace, behind `front` bytes of the caller's own (a multiple of 16)
+inline size_t pad16(size_t v) { return (v + 15) / 16 * 16; }
+
+struct SortLayout {
+    size_t rows, cell_of, start, pop, bytes;
+    int64_t cells;
+};
+// false where the shape is not served: total outside 1 .. max_total, or B * cells_per_tile outside 1 .. 2^22
+inline bool sort_layout(int64_t total, int64_t max_total, int64_t B, int64_t cells_per_tile, size_t front, SortLayout& L) {
+    if (total < 1 || total > max_total || B < 1 || cells_per_tile < 1 || B > kMaxCells || cells_per_tile > kMaxCells ||
+        B * cells_per_tile > kMaxCells)
+        return false;
+    const size_t T = (size_t)total;
+    L.cells = B * cells_per_tile;
+    size_t at = front;
+    L.rows = at, at += T * sizeof(Row);
+    L.cell_of = at, at += pad16(T * 4);
+    L.start = at, at += pad16(((size_t)L.cells + 1) * 4);
+    L.pop = at, at += pad16((size_t)L.cells * 4);
+    L.bytes = at;
+    return true;
+}
+
+// The checks of a call's radius, dims and mult, in two steps because the calls refuse their other arguments in between
+// (what is invalid before what is not served).  First the values that mean nothing ...
+inline int grid_args_valid(const char* who, double radius, int dim_x, int dim_y, int dim_z, int64_t mult) {
+    if (!(radius > 0.0) || !std::isfinite(radius))
+        return sn::fail(SN_ERR_INVALID_ARG, "%s: radius must be positive and finite", who);
+    if (dim_x < 1 || dim_y < 1 || dim_z < 1 || mult < 1)
+        return sn::fail(SN_ERR_INVALID_ARG, "%s: dims and mult must be at least 1 (got %d, %d, %d; %lld)", who, dim_x, dim_y,
+                        dim_z, (long long)mult);
+    return SN_OK;
+}
+// ... then the cell budget and the range of radius, and the grid of one tile (its lo is read per tile on the device)
+inline int grid_of_tiles(const char* who, double radius, int B, int dim_x, int dim_y, int dim_z, int64_t mult, CellGrid& g) {
+    const int64_t cpt = (int64_t)dim_x * dim_y;   // (each factor < 2^31: no overflow before the checks)
+    if (cpt > kMaxCells || cpt * dim_z > kMaxCells || cpt * dim_z * B > kMaxCells)
+        return sn::fail(SN_ERR_UNSUPPORTED, "%s: more than 2^22 cells (B * dims = %d * %d * %d * %d)", who, B, dim_x, dim_y, dim_z);
+    if (radius < kEpsMin || radius > kEpsMax)
+        return sn::fail(SN_ERR_UNSUPPORTED, "%s: radius beyond what is served (1e-150 .. 1e150)", who);
+    const double side = cell_side((double)mult, radius);
+    if (!std::isfinite(side)) return sn::fail(SN_ERR_UNSUPPORTED, "%s: mult * radius is not finite", who);
+    g.lo[0] = g.lo[1] = g.lo[2] = 0.0;
+    g.inv = 1.0 / side;
+    g.dim[0] = dim_x, g.dim[1] = dim_y, g.dim[2] = dim_z;
+    g.cells = (int)(cpt * dim_z);   // per tile
+    return SN_OK;
 }
 
 }  // namespace

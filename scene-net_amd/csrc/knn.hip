@@ -11,7 +11,9 @@
 // function of the candidate SET: the list is ordered by a total order on (d2, row), found is a count.
 //
 // The rows are counting-sorted into the cell grid of cell_grid.h, with eps = radius and k = mult, from each tile's own lo:
-// the cell key is tile * cells_per_tile + local cell, so tiles never meet; a Row is (x, y, z, row index, key).
+// the cell key is tile * cells_per_tile + local cell, so tiles never meet; a Row is (x, y, z, row index, key).  The sort is
+// cell_grid.h's text (the bodies of launches 1 to 3, the layout of its arrays, the checks of the grid's arguments), which
+// shape.hip runs too; the kernels are this file's, so that a trace tells the two calls apart.
 //   1 cells    tile (binary search in offsets) and cell of every row, populations (integer atomics, zeroed by a small
 //              launch in front); rows that no tile owns get their empty result here
 //   2 prefix   cell_starts
@@ -25,6 +27,7 @@
 // Bound: launch 4 by the latency of the candidate loads, as K10's launches 4, 5 and 8.
 #include "common.h"
 #include "cell_grid.h"
+#include "packed_rows.h"
 #include "scan.h"
 #include <cmath>
 
@@ -35,30 +38,13 @@ constexpr int kChunk = kThreads;        // rows per workgroup of launches 1, 3, 
 constexpr int kStatParts = 128;         // workgroups per tile of the partials kernel
 constexpr int kMaxK = SN_KNN_MAX_K;
 
-__device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// rows that tiles own: offsets[B] clamped into 0 .. total
-__device__ __forceinline__ int live_rows(const int64_t* __restrict__ offsets, int B, int total) {
-    const int64_t m = offsets[B];
-    return m <= 0 ? 0 : (m < total ? (int)m : total);
-}
-
-// the tile of packed row i: the last b in 0 .. B-1 with offsets[b] <= i (empty tiles are skipped by construction)
-__device__ __forceinline__ int tile_of_row(const int64_t* __restrict__ offsets, int B, int64_t i) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (offsets[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
+using sn::live_rows;   // packed_rows.h
+using sn::pos_inf;
+using sn::quiet_nan;
 
 // ---- 0: the populations zeroed by a launch of this file, not by a memset node ("Launches")
 __global__ __launch_bounds__(kThreads) void knn_zero_kernel(int32_t* __restrict__ pop, int cells) {
-    const int c = blockIdx.x * kThreads + threadIdx.x;
-    if (c < cells) pop[c] = 0;
+    zero_population(pop, cells, blockIdx.x * kThreads + threadIdx.x);
 }
 
 // ---- 1: the cell key of every row and the cells' populations; the empty result of rows outside every tile
@@ -80,13 +66,7 @@ __global__ __launch_bounds__(kThreads) void knn_cells_kernel(const double* __res
         if (mean_dist) mean_dist[i] = quiet_nan();
         return;
     }
-    const int b = tile_of_row(offsets, B, i);
-    CellGrid t = g;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t.lo[a] = lo[(size_t)b * 3 + a];
-    const int c = b * g.cells + cell_of_point(t, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2]);
-    cell_of[i] = c;
-    atomicAdd(pop + c, 1);
+    count_packed_row(pts, offsets, B, lo, g, i, cell_of, pop);
 }
 
 // ---- 2: one workgroup: the cells' starts and cursors
@@ -103,14 +83,7 @@ __global__ __launch_bounds__(kThreads) void knn_scatter_kernel(const double* __r
                                                                int32_t* __restrict__ cursor, Row* __restrict__ rows) {
     const int m = live_rows(offsets, B, total);
     const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= m) return;
-    Row r;
-    r.x = pts[(size_t)i * 3];
-    r.y = pts[(size_t)i * 3 + 1];
-    r.z = pts[(size_t)i * 3 + 2];
-    r.pos = i;
-    r.cell = cell_of[i];
-    scatter_row(r, m, cursor, rows);
+    if (i < m) scatter_packed_row(pts, i, m, cell_of, cursor, rows);
 }
 
 // ---- 4: the search.  (v, p) sorts in front of (d, i) iff v < d, or v == d and p < i
@@ -306,26 +279,12 @@ __global__ __launch_bounds__(kThreads) void knn_stat_combine_kernel(const int64_
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-struct Layout {
-    size_t rows, cell_of, start, pop, partials, bytes;
-    int64_t cells, n_slots;
-};
-bool layout_of(int64_t total, int64_t B, int64_t cells_per_tile, Layout& L) {
-    if (total < 1 || total >= ((int64_t)1 << 31) || B < 1 || cells_per_tile < 1 || B > kMaxCells || cells_per_tile > kMaxCells ||
-        B * cells_per_tile > kMaxCells)
-        return false;
-    const size_t T = (size_t)total;
-    auto pad = [](size_t v) { return (v + 15) / 16 * 16; };
-    L.cells = B * cells_per_tile;
-    L.n_slots = total / kChunk + B + 1;
-    size_t at = 0;
-    L.partials = at, at += pad((size_t)L.n_slots * kStat * 8);   // in front: sn_knn_tile_stats finds it without the grid
-    L.rows = at, at += T * sizeof(Row);
-    L.cell_of = at, at += pad(T * 4);
-    L.start = at, at += pad(((size_t)L.cells + 1) * 4);
-    L.pop = at, at += pad((size_t)L.cells * 4);
-    L.bytes = at;
-    return true;
+// the statistics partials lead the workspace, the sort's arrays (cell_grid.h) behind them: sn_knn_tile_stats finds its
+// slots without the grid
+int64_t stat_slots(int64_t total, int64_t B) { return total / kChunk + B + 1; }
+size_t partials_bytes(int64_t total, int64_t B) { return pad16((size_t)stat_slots(total, B) * kStat * 8); }
+bool layout_of(int64_t total, int64_t B, int64_t cells_per_tile, SortLayout& L) {
+    return sort_layout(total, ((int64_t)1 << 31) - 1, B, cells_per_tile, partials_bytes(total, B), L);
 }
 
 template <int K>
@@ -345,35 +304,21 @@ int run(const double* pts, const int64_t* offsets, int64_t total, int B, double 
     if (total <= 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: total must be positive (got %lld)", who, (long long)total);
     if (B <= 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: B must be positive (got %d)", who, B);
     if (k < 1) return sn::fail(SN_ERR_INVALID_ARG, "%s: k must be at least 1 (got %d)", who, k);
-    if (!(radius > 0.0) || !std::isfinite(radius))
-        return sn::fail(SN_ERR_INVALID_ARG, "%s: radius must be positive and finite", who);
-    if (dim_x < 1 || dim_y < 1 || dim_z < 1 || mult < 1)
-        return sn::fail(SN_ERR_INVALID_ARG, "%s: dims and mult must be at least 1 (got %d, %d, %d; %lld)", who, dim_x, dim_y,
-                        dim_z, (long long)mult);
+    if (int e = grid_args_valid(who, radius, dim_x, dim_y, dim_z, mult)) return e;
     if (flags & ~SN_KNN_EXCLUDE_ZERO) return sn::fail(SN_ERR_INVALID_ARG, "%s: unknown flags %d", who, flags);
     if (k > kMaxK) return sn::fail(SN_ERR_UNSUPPORTED, "%s: k beyond what is served (at most %d, got %d)", who, kMaxK, k);
     if (total >= ((int64_t)1 << 31)) return sn::fail(SN_ERR_UNSUPPORTED, "%s: total < 2^31 rows are served", who);
-    const int64_t cpt = (int64_t)dim_x * dim_y;   // (each factor < 2^31: no overflow before the checks)
-    if (cpt > kMaxCells || cpt * dim_z > kMaxCells || cpt * dim_z * B > kMaxCells)
-        return sn::fail(SN_ERR_UNSUPPORTED, "%s: more than 2^22 cells (B * dims = %d * %d * %d * %d)", who, B, dim_x, dim_y, dim_z);
-    if (radius < kEpsMin || radius > kEpsMax)
-        return sn::fail(SN_ERR_UNSUPPORTED, "%s: radius beyond what is served (1e-150 .. 1e150)", who);
-    const double side = cell_side((double)mult, radius);
-    if (!std::isfinite(side)) return sn::fail(SN_ERR_UNSUPPORTED, "%s: mult * radius is not finite", who);
+    CellGrid g;
+    if (int e = grid_of_tiles(who, radius, B, dim_x, dim_y, dim_z, mult, g)) return e;
     if ((uintptr_t)pts % 8 || (uintptr_t)offsets % 8 || (uintptr_t)lo % 8 || (uintptr_t)ws % 16 || (uintptr_t)d2 % 8 ||
         (uintptr_t)found % 4 || (uintptr_t)mean_dist % 8 || (uintptr_t)index % 8)
         return sn::fail(SN_ERR_INVALID_ARG, "%s: pts / offsets / lo / d2 / mean_dist / index must be 8-byte aligned, ws "
                         "16-byte, found 4-byte", who);
-    Layout L;
-    layout_of(total, B, cpt * dim_z, L);
+    SortLayout L;
+    layout_of(total, B, g.cells, L);
     if (ws_bytes < L.bytes)
         return sn::fail(SN_ERR_INVALID_ARG, "%s: ws holds %zu bytes, %zu needed (sn_knn_ws_bytes)", who, ws_bytes, L.bytes);
 
-    CellGrid g;
-    g.lo[0] = g.lo[1] = g.lo[2] = 0.0;   // (per tile, read from lo on the device)
-    g.inv = 1.0 / side;
-    g.dim[0] = dim_x, g.dim[1] = dim_y, g.dim[2] = dim_z;
-    g.cells = (int)(cpt * dim_z);        // per tile
     hipStream_t s = sn::as_stream(stream);
     char* w = static_cast<char*>(ws);
     Row* rows = reinterpret_cast<Row*>(w + L.rows);
@@ -416,7 +361,7 @@ int run(const double* pts, const int64_t* offsets, int64_t total, int B, double 
 extern "C" int sn_knn_chunk_points(void) { return kChunk; }
 
 extern "C" size_t sn_knn_ws_bytes(int64_t total, int B, int64_t cells_per_tile) {
-    Layout L;
+    SortLayout L;
     return layout_of(total, B, cells_per_tile, L) ? L.bytes : 0;
 }
 
@@ -451,17 +396,16 @@ extern "C" int sn_knn_tile_stats(const double* mean_dist, const int32_t* found, 
     if ((uintptr_t)mean_dist % 8 || (uintptr_t)found % 4 || (uintptr_t)offsets % 8 || (uintptr_t)ws % 16 || (uintptr_t)stats % 8)
         return sn::fail(SN_ERR_INVALID_ARG, "%s: mean_dist / offsets / stats must be 8-byte aligned, ws 16-byte, found 4-byte",
                         who);
-    Layout L;
-    layout_of(total, B, 1, L);   // (the partials lead the workspace whatever the grid is)
-    const size_t need = L.rows;
+    const size_t need = partials_bytes(total, B);   // (the partials lead the workspace whatever the grid is)
+    const int64_t n_slots = stat_slots(total, B);
     if (ws_bytes < need)
         return sn::fail(SN_ERR_INVALID_ARG, "%s: ws holds %zu bytes, %zu needed (sn_knn_ws_bytes)", who, ws_bytes, need);
     hipStream_t s = sn::as_stream(stream);
     double* partials = static_cast<double*>(ws);
     hipLaunchKernelGGL(knn_stat_partials_kernel, dim3(kStatParts, (unsigned)B), dim3(kThreads), 0, s, mean_dist, found, offsets,
-                       total, k, partials, L.n_slots);
+                       total, k, partials, n_slots);
     if (int e = sn::check_launch("sn_knn_tile_stats(partials)")) return e;
-    hipLaunchKernelGGL(knn_stat_combine_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, offsets, total, partials, L.n_slots,
+    hipLaunchKernelGGL(knn_stat_combine_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, offsets, total, partials, n_slots,
                        stats);
     return sn::check_launch("sn_knn_tile_stats(combine)");
 }

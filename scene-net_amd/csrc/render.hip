@@ -10,8 +10,8 @@
 //   s x s pixels around it by unsigned 64-bit minimum.  Nearest depth wins, the lowest row among equal quanta.
 //
 // Shape, splat: kRenderThreads = 256 threads per workgroup, one thread per row of the packed batch, the tiles that reach
-// into the workgroup's 256 rows walked one at a time (K18's walk), so the test "is view k a view of this tile" and every
-// camera read is uniform (scalar loads).  A row is read once and kept in registers for all its views.
+// into the workgroup's 256 rows walked one at a time (the walk of sn::for_tiles, packed_rows.h, written out), so the test
+// "is view k a view of this tile" and every camera read is uniform (scalar loads).  A row is read once and kept in registers for all its views.
 //   clear     keys <- all ones, count <- 0, bad_views <- 0 (one kernel, no memset node: voxel_classes.hip, zero_kernel);
 //             left out with SN_RENDER_ACCUMULATE
 //   splat     per pixel of a splat of s >= 2 a relaxed agent-scope load, the 64-bit atomic min only where the load shows
@@ -27,6 +27,7 @@
 // Bound: splat reads 24 B per row once; per view and accepted row it looks at s*s pixels (8 B each) and sends at most as
 // many atomics.  resolve reads 8 B (40 B with shading) and writes 4 to 16 B per pixel.
 #include "common.h"
+#include "packed_rows.h"
 
 namespace {
 
@@ -38,16 +39,6 @@ constexpr unsigned long long kMaxQuantum = 0xffffffffull;
 constexpr int64_t kMaxTileRows = 0xffffffffll;               // a tile of this many rows or more is not drawn
 constexpr double kTwo32 = 4294967296.0;
 constexpr double kPixelLimit = 1073741824.0;                 // |px|, |py| < 2^30
-
-// first tile whose rows can reach row `base`: the largest b with offsets[b] <= base (0 if there is none)
-__device__ __forceinline__ int tile_of(const int64_t* __restrict__ offsets, int B, int64_t base) {
-    int lo = 0, hi = B;   // first b in [0, B) with offsets[b] > base
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] > base) hi = mid; else lo = mid + 1;
-    }
-    return lo > 0 ? lo - 1 : 0;
-}
 
 // the header's list of camera rows that show nothing (every comparison is false for a NaN)
 __device__ __forceinline__ bool camera_ok(const double* __restrict__ c) {
@@ -86,7 +77,9 @@ __global__ __launch_bounds__(kRenderThreads) void render_splat_kernel(const doub
     const int64_t end = base + kRenderThreads < total ? base + kRenderThreads : total;
     const int64_t i = base + t;
     const size_t image = (size_t)H * (size_t)W;
-    for (int b = tile_of(offsets, B, base); b < B; ++b) {
+    // sn::for_tiles (packed_rows.h) written out: through it the splat of the C2 batch measured 1 to 2 % slower than this
+    // loop, its resolve in the same runs not
+    for (int b = sn::tile_of(offsets, B, base); b < B; ++b) {
         const int64_t lo = offsets[b], hi = offsets[b + 1];
         if (lo >= end) break;
         const int64_t from = lo > base ? lo : base, to = hi < end ? hi : end;

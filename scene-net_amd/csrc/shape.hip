@@ -11,7 +11,9 @@
 // and the order of the rows in the array do not show in any bit.  Covariance, cyclic Jacobi with SN_SHAPE_SWEEPS sweeps,
 // the sort, the sign rule and the features are fp64 operations rounded once each, + - * / sqrt only, in the header's order.
 //
-// The rows are counting-sorted into the cell grid of cell_grid.h exactly as knn.hip sorts them, by launches of this file:
+// The rows are counting-sorted into the cell grid of cell_grid.h exactly as knn.hip sorts them -- one text there for the
+// bodies of launches 0 to 3, the layout of the sort's arrays and the checks of the grid's arguments -- by launches of this
+// file, so that a trace tells the two calls apart:
 //   0 zero     the cells' populations (a kernel, not a memset node: DESIGN section 7 K21, "Launches")
 //   1 cells    tile and cell of every row, populations (integer atomics); rows that no tile owns get their empty result
 //   2 prefix   cell_starts
@@ -19,12 +21,13 @@
 //   4 shape    one thread per row IN CELL ORDER: the 9 runs of the 27 cells as knn_search_kernel walks them, count and
 //              the nine moments in registers (32 x 32 -> 64-bit multiply-adds), then the solver in registers, results
 //              stored at the row's own index
-// live_rows and tile_of_row are private copies of knn.hip's (that file and cell_grid.h are not touched: K10 and K21 build
-// to the code they had).
+// The 9-run candidate loop of launch 4 is written out here as in knn_search_kernel: it ran slower through a callback, per
+// row and per run.
 //
 // Bound: launch 4 by the latency of the candidate loads, as K21's launch 4.
 #include "common.h"
 #include "cell_grid.h"
+#include "packed_rows.h"
 #include "scan.h"
 #include <cmath>
 
@@ -35,24 +38,8 @@ constexpr int kChunk = kThreads;   // rows per workgroup of launches 1, 3, 4
 constexpr int kSweeps = SN_SHAPE_SWEEPS;
 constexpr int kFeat = SN_SHAPE_NFEAT;
 
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// rows that tiles own: offsets[B] clamped into 0 .. total
-__device__ __forceinline__ int live_rows(const int64_t* __restrict__ offsets, int B, int total) {
-    const int64_t m = offsets[B];
-    return m <= 0 ? 0 : (m < total ? (int)m : total);
-}
-
-// the tile of packed row i: the last b in 0 .. B-1 with offsets[b] <= i (empty tiles are skipped by construction)
-__device__ __forceinline__ int tile_of_row(const int64_t* __restrict__ offsets, int B, int64_t i) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (offsets[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
+using sn::live_rows;   // packed_rows.h
+using sn::quiet_nan;
 
 struct Outputs {
     int32_t* count;
@@ -77,8 +64,7 @@ __device__ __forceinline__ void store_nan(const Outputs& o, size_t i) {
 
 // ---- 0: the populations zeroed by a launch of this file
 __global__ __launch_bounds__(kThreads) void shape_zero_kernel(int32_t* __restrict__ pop, int cells) {
-    const int c = blockIdx.x * kThreads + threadIdx.x;
-    if (c < cells) pop[c] = 0;
+    zero_population(pop, cells, blockIdx.x * kThreads + threadIdx.x);
 }
 
 // ---- 1: the cell key of every row and the cells' populations; the empty result of rows outside every tile
@@ -99,13 +85,7 @@ __global__ __launch_bounds__(kThreads) void shape_cells_kernel(const double* __r
         store_nan(o, (size_t)i);
         return;
     }
-    const int b = tile_of_row(offsets, B, i);
-    CellGrid t = g;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t.lo[a] = lo[(size_t)b * 3 + a];
-    const int c = b * g.cells + cell_of_point(t, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2]);
-    cell_of[i] = c;
-    atomicAdd(pop + c, 1);
+    count_packed_row(pts, offsets, B, lo, g, i, cell_of, pop);
 }
 
 // ---- 2: one workgroup: the cells' starts and cursors
@@ -122,14 +102,7 @@ __global__ __launch_bounds__(kThreads) void shape_scatter_kernel(const double* _
                                                                  int32_t* __restrict__ cursor, Row* __restrict__ rows) {
     const int m = live_rows(offsets, B, total);
     const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= m) return;
-    Row r;
-    r.x = pts[(size_t)i * 3];
-    r.y = pts[(size_t)i * 3 + 1];
-    r.z = pts[(size_t)i * 3 + 2];
-    r.pos = i;
-    r.cell = cell_of[i];
-    scatter_row(r, m, cursor, rows);
+    if (i < m) scatter_packed_row(pts, i, m, cell_of, cursor, rows);
 }
 
 // ---- 4: the moments and the solver
@@ -270,24 +243,9 @@ __global__ __launch_bounds__(kThreads) void shape_moments_kernel(const int64_t* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-struct Layout {
-    size_t rows, cell_of, start, pop, bytes;
-    int64_t cells;
-};
-bool layout_of(int64_t total, int64_t B, int64_t cells_per_tile, Layout& L) {
-    if (total < 1 || total > ((int64_t)1 << 30) || B < 1 || cells_per_tile < 1 || B > kMaxCells || cells_per_tile > kMaxCells ||
-        B * cells_per_tile > kMaxCells)
-        return false;
-    const size_t T = (size_t)total;
-    auto pad = [](size_t v) { return (v + 15) / 16 * 16; };
-    L.cells = B * cells_per_tile;
-    size_t at = 0;
-    L.rows = at, at += T * sizeof(Row);
-    L.cell_of = at, at += pad(T * 4);
-    L.start = at, at += pad(((size_t)L.cells + 1) * 4);
-    L.pop = at, at += pad((size_t)L.cells * 4);
-    L.bytes = at;
-    return true;
+// the workspace is the sort's arrays (cell_grid.h) and nothing else
+bool layout_of(int64_t total, int64_t B, int64_t cells_per_tile, SortLayout& L) {
+    return sort_layout(total, (int64_t)1 << 30, B, cells_per_tile, 0, L);
 }
 
 int run(const double* pts, const int64_t* offsets, int64_t total, int B, double radius, int min_points, int flags,
@@ -299,35 +257,21 @@ int run(const double* pts, const int64_t* offsets, int64_t total, int B, double 
     if (total <= 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: total must be positive (got %lld)", who, (long long)total);
     if (B <= 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: B must be positive (got %d)", who, B);
     if (min_points < 3) return sn::fail(SN_ERR_INVALID_ARG, "%s: min_points must be at least 3 (got %d)", who, min_points);
-    if (!(radius > 0.0) || !std::isfinite(radius))
-        return sn::fail(SN_ERR_INVALID_ARG, "%s: radius must be positive and finite", who);
-    if (dim_x < 1 || dim_y < 1 || dim_z < 1 || mult < 1)
-        return sn::fail(SN_ERR_INVALID_ARG, "%s: dims and mult must be at least 1 (got %d, %d, %d; %lld)", who, dim_x, dim_y,
-                        dim_z, (long long)mult);
+    if (int e = grid_args_valid(who, radius, dim_x, dim_y, dim_z, mult)) return e;
     if (flags != 0) return sn::fail(SN_ERR_INVALID_ARG, "%s: unknown flags %d (none are defined)", who, flags);
     if (total > ((int64_t)1 << 30))
         return sn::fail(SN_ERR_UNSUPPORTED, "%s: total <= 2^30 rows are served (the moments stay inside int64)", who);
-    const int64_t cpt = (int64_t)dim_x * dim_y;   // (each factor < 2^31: no overflow before the checks)
-    if (cpt > kMaxCells || cpt * dim_z > kMaxCells || cpt * dim_z * B > kMaxCells)
-        return sn::fail(SN_ERR_UNSUPPORTED, "%s: more than 2^22 cells (B * dims = %d * %d * %d * %d)", who, B, dim_x, dim_y, dim_z);
-    if (radius < kEpsMin || radius > kEpsMax)
-        return sn::fail(SN_ERR_UNSUPPORTED, "%s: radius beyond what is served (1e-150 .. 1e150)", who);
-    const double side = cell_side((double)mult, radius);
-    if (!std::isfinite(side)) return sn::fail(SN_ERR_UNSUPPORTED, "%s: mult * radius is not finite", who);
+    CellGrid g;
+    if (int e = grid_of_tiles(who, radius, B, dim_x, dim_y, dim_z, mult, g)) return e;
     if ((uintptr_t)pts % 8 || (uintptr_t)offsets % 8 || (uintptr_t)lo % 8 || (uintptr_t)ws % 16 || (uintptr_t)count % 4 ||
         (uintptr_t)moments % 8 || (uintptr_t)eig % 8 || (uintptr_t)normal % 8 || (uintptr_t)axis % 8 || (uintptr_t)feat % 8)
         return sn::fail(SN_ERR_INVALID_ARG, "%s: pts / offsets / lo / moments / eig / normal / axis / feat must be 8-byte "
                         "aligned, ws 16-byte, count 4-byte", who);
-    Layout L;
-    layout_of(total, B, cpt * dim_z, L);
+    SortLayout L;
+    layout_of(total, B, g.cells, L);
     if (ws_bytes < L.bytes)
         return sn::fail(SN_ERR_INVALID_ARG, "%s: ws holds %zu bytes, %zu needed (sn_shape_ws_bytes)", who, ws_bytes, L.bytes);
 
-    CellGrid g;
-    g.lo[0] = g.lo[1] = g.lo[2] = 0.0;   // (per tile, read from lo on the device)
-    g.inv = 1.0 / side;
-    g.dim[0] = dim_x, g.dim[1] = dim_y, g.dim[2] = dim_z;
-    g.cells = (int)(cpt * dim_z);        // per tile
     hipStream_t s = sn::as_stream(stream);
     char* w = static_cast<char*>(ws);
     Row* rows = reinterpret_cast<Row*>(w + L.rows);
@@ -371,7 +315,7 @@ int run(const double* pts, const int64_t* offsets, int64_t total, int B, double 
 extern "C" int sn_shape_chunk_points(void) { return kChunk; }
 
 extern "C" size_t sn_shape_ws_bytes(int64_t total, int B, int64_t cells_per_tile) {
-    Layout L;
+    SortLayout L;
     return layout_of(total, B, cells_per_tile, L) ? L.bytes : 0;
 }
 

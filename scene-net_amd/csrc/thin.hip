@@ -10,9 +10,10 @@
 // the point's place in ITS tile, never of the batch or of scheduling.
 //
 // Shape: K9's, its scans and ranks from scan.h -- one WAVE per workgroup, kWaveChunk = 1024 consecutive rows of the packed
-// batch per workgroup, lane l holding the rows chunk * 1024 + g * 64 + l, g = 0..15.  A chunk may straddle tiles: the wave finds the tile of its first row by
-// a bisection of offsets (wave-uniform, scalar loads) and walks the tiles that reach into the chunk, one edge table in LDS
-// at a time (one wave: the barrier around the reload costs nothing).
+// batch per workgroup, lane l holding the rows chunk * 1024 + g * 64 + l, g = 0..15.  A chunk may straddle tiles: the wave
+// finds the tile of its first row by a bisection of offsets (wave-uniform, scalar loads) and walks the tiles that reach
+// into the chunk (the walk of sn::for_tiles, packed_rows.h, which K18 and K24 call; written out in decide_chunk),
+// one edge table in LDS at a time (one wave: the barrier around the reload costs nothing).
 //   count:    the decision of every row -> ws.keep[chunk][16] (one 64-bit ballot per group), ws.unb[chunk][16] (rows that
 //             no table holds), their popcounts in ws.kept[chunk] / ws.lost[chunk]; `first` by 64-bit atomic min (the z
 //             rule's through nz words of LDS per wave; without groups it is one plain store per tile)
@@ -28,6 +29,7 @@
 // gathered 8 B of thr; scatter reads 24 + 8 B and writes 24 + 8 + 8 (+ 4) B per kept row.
 #include "common.h"
 #include "binning.h"
+#include "packed_rows.h"
 #include "scan.h"
 
 namespace {
@@ -78,16 +80,6 @@ struct Rule {
     const int64_t* tile_ids;    // [B] | null
 };
 
-// first tile whose rows can reach row `base`: the largest b with offsets[b] <= base (0 if there is none)
-__device__ __forceinline__ int tile_of(const int64_t* __restrict__ offsets, int B, int64_t base) {
-    int lo = 0, hi = B;   // first b in [0, B) with offsets[b] > base
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] > base) hi = mid; else lo = mid + 1;
-    }
-    return lo > 0 ? lo - 1 : 0;
-}
-
 // 64-bit atomic min, sent only where it would lower the slot (a stale look is a larger value: nothing is lost)
 __device__ __forceinline__ void first_min(unsigned long long* slot, unsigned long long j) {
     if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > j)
@@ -110,7 +102,9 @@ __device__ __forceinline__ void decide_chunk(const Rule& R, int64_t base, int la
     const uint64_t seed = R.seed ? *R.seed : 0ull;
     const int ne = R.nx + R.ny + R.nz + 3;
     const int plane = R.nx * R.ny;
-    for (int b = tile_of(R.offsets, R.B, base); b < R.B; ++b) {
+    // sn::for_tiles (packed_rows.h) written out: through it thin_count_kernel<SN_THIN_GROUP_VOXEL> takes 130 VGPRs, not 128,
+    // and runs 3 waves per SIMD, not 4
+    for (int b = sn::tile_of(R.offsets, R.B, base); b < R.B; ++b) {
         const int64_t lo = R.offsets[b], hi = R.offsets[b + 1];
         if (lo >= end) break;
         const int64_t from = lo > base ? lo : base, to = hi < end ? hi : end;

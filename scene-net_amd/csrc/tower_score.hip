@@ -18,9 +18,12 @@
 //
 // Bound: launch latency.  The data of a tile is K * 96 bytes.
 #include "common.h"
+#include "packed_rows.h"
 #include <cmath>
 
 namespace {
+
+using sn::quiet_nan;   // packed_rows.h: the bit pattern K21 and K22 store too
 
 constexpr int kThreads = 256;
 constexpr int kSumThreads = 1024;
@@ -51,8 +54,6 @@ __device__ __forceinline__ double extent_of(const long long* r, const Geom& g, i
 __device__ __forceinline__ int rows_of(int n_towers, int K) {   // the rows that can be present
     return n_towers < 0 ? 0 : (n_towers < K ? n_towers : K);
 }
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---- centroids: one workgroup per tile
 __global__ __launch_bounds__(kThreads) void tscore_centroids_kernel(const long long* __restrict__ stats,

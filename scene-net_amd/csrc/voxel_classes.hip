@@ -11,9 +11,10 @@
 // c; the row's colour is table[rank].
 //
 // Shape, grid: thin.hip's -- one WAVE per workgroup, kWaveChunk = 1024 consecutive rows of the packed batch, the tiles that
-// reach into the chunk walked one edge table in LDS at a time.  A label becomes the order-preserving key of common.h
-// (enc_f64): every key of a value that is not NaN is >= 0x000FFFFFFFFFFFFF (-inf), which leaves 0 for "empty" and 1 for "NaN
-// labels only".  The keys live in the grid's own cells:
+// reach into the chunk walked (sn::for_tiles, packed_rows.h; census and paint walk their chunks with it too) one edge table
+// in LDS at a time.  A label becomes the order-preserving key of common.h (enc_f64): every key of a value that is not NaN
+// is >= 0x000FFFFFFFFFFFFF (-inf), which leaves 0 for "empty" and 1 for "NaN labels only".  The keys live in the grid's
+// own cells:
 //   zero      grid, unbinned, nan_labels <- 0 (one kernel, no memset node: see zero_kernel)
 //   points    one 64-bit integer atomic max per binned row, sent only where a plain load of the cell shows less than the
 //             row's key (the cell only grows: a stale look costs a needless atomic, never a result)
@@ -32,6 +33,7 @@
 // reads 8 B per row; paint reads 8 B and writes 24 B (colors) and / or 6 B (rgb) per row.
 #include "common.h"
 #include "binning.h"
+#include "packed_rows.h"
 #include "scan.h"
 
 namespace {
@@ -52,16 +54,6 @@ constexpr int kClassItems = kClassWords / kClassThreads;    // words per thread 
 constexpr int kClassBatch = 8;                              // rows per thread whose loads are in flight together
 static_assert(kClassRounds % kClassBatch == 0, "whole batches");
 static_assert(kClassItems * kClassThreads == kClassWords, "one scan tile holds the bitmap");
-
-// first tile whose rows can reach row `base`: the largest b with offsets[b] <= base (0 if there is none)
-__device__ __forceinline__ int tile_of(const int64_t* __restrict__ offsets, int B, int64_t base) {
-    int lo = 0, hi = B;   // first b in [0, B) with offsets[b] > base
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] > base) hi = mid; else lo = mid + 1;
-    }
-    return lo > 0 ? lo - 1 : 0;
-}
 
 // p[0 .. n) <- 0 (the grid's keys, a tile's bitmap) and c0[0 .. m), c1[0 .. m) <- 0 (the per-tile counters the kernels
 // behind it add into; c1 nullable), in one launch.  A kernel, not memset nodes: [measured] with several memset nodes in one
@@ -95,14 +87,9 @@ __global__ __launch_bounds__(kWaveLanes) void classes_points_kernel(const double
     extern __shared__ double edges[];
     const int lane = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * kWaveChunk;
-    const int64_t end = base + kWaveChunk < total ? base + kWaveChunk : total;
     const int ne = nx + ny + nz + 3;
     const int64_t V = (int64_t)nx * ny * nz;
-    for (int b = tile_of(offsets, B, base); b < B; ++b) {
-        const int64_t lo = offsets[b], hi = offsets[b + 1];
-        if (lo >= end) break;
-        const int64_t from = lo > base ? lo : base, to = hi < end ? hi : end;
-        if (from >= to) continue;   // an empty tile, or one that ends before the chunk
+    sn::for_tiles(offsets, B, base, kWaveChunk, total, [&](int b, int64_t, int64_t, int64_t from, int64_t to) {
         const double* d = desc + (size_t)b * (size_t)(6 + ne);
         __syncthreads();   // the previous tile's table has been read
         sn::load_edges(edges, d, ne, kWaveLanes);
@@ -135,7 +122,7 @@ __global__ __launch_bounds__(kWaveLanes) void classes_points_kernel(const double
             if (nunb) __hip_atomic_fetch_add(unbinned + b, (unsigned long long)nunb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (nnan) __hip_atomic_fetch_add(nan_labels + b, (unsigned long long)nnan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    }
+    });
 }
 
 // keys -> labels, in place
@@ -166,12 +153,7 @@ __global__ __launch_bounds__(kClassThreads) void class_census_kernel(const doubl
     __shared__ uint32_t s_bits[kClassWords];
     const int t = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * kClassChunk;
-    const int64_t end = base + kClassChunk < total ? base + kClassChunk : total;
-    for (int b = tile_of(offsets, B, base); b < B; ++b) {
-        const int64_t lo = offsets[b], hi = offsets[b + 1];
-        if (lo >= end) break;
-        const int64_t from = lo > base ? lo : base, to = hi < end ? hi : end;
-        if (from >= to) continue;
+    sn::for_tiles(offsets, B, base, kClassChunk, total, [&](int b, int64_t, int64_t, int64_t from, int64_t to) {
         __syncthreads();   // the previous tile's bitmap has been merged
         for (int w = t; w < kClassWords; w += kClassThreads) s_bits[w] = 0u;
         __syncthreads();
@@ -207,7 +189,7 @@ __global__ __launch_bounds__(kClassThreads) void class_census_kernel(const doubl
             const uint32_t v = s_bits[w];
             if (v) __hip_atomic_fetch_or(mine + w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    }
+    });
 }
 
 // thread t's kClassItems consecutive words of a tile's bitmap and the exclusive prefix of their popcounts; returns the
@@ -270,12 +252,7 @@ __global__ __launch_bounds__(kClassThreads) void class_paint_kernel(const double
     __shared__ int s_wave[kClassThreads / 64];
     const int t = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * kClassChunk;
-    const int64_t end = base + kClassChunk < total ? base + kClassChunk : total;
-    for (int b = tile_of(offsets, B, base); b < B; ++b) {
-        const int64_t lo = offsets[b], hi = offsets[b + 1];
-        if (lo >= end) break;
-        const int64_t from = lo > base ? lo : base, to = hi < end ? hi : end;
-        if (from >= to) continue;
+    sn::for_tiles(offsets, B, base, kClassChunk, total, [&](int b, int64_t, int64_t, int64_t from, int64_t to) {
         __syncthreads();   // the previous tile's tables have been read
         {
             uint32_t w[kClassItems];
@@ -333,7 +310,7 @@ __global__ __launch_bounds__(kClassThreads) void class_paint_kernel(const double
         nshort = sn::wave_reduce(nshort, [](int a, int b) { return a + b; });
         if ((t & 63) == 0 && nshort)
             __hip_atomic_fetch_add(short_table + b, (unsigned long long)nshort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    });
 }
 
 bool shape_served(int64_t total, int B) { return total > 0 && B > 0 && total <= kMaxTotal && B <= kMaxB; }

@@ -11,8 +11,8 @@
 // depend on scheduling or on the order of the rows.
 //
 // Shape: voxel_classes.hip's -- one WAVE per workgroup, kWaveChunk = 1024 consecutive rows of the packed batch, the tiles
-// that reach into the chunk walked one edge table in LDS at a time; next to the table the tile's quantisers (lo, inv per
-// plane), formed by the first P lanes.
+// that reach into the chunk walked (sn::for_tiles, packed_rows.h) one edge table in LDS at a time; next to the table the
+// tile's quantisers (lo, inv per plane), formed by the first P lanes.
 //   clear     accumulators <- what each reduction starts from (0 for a count, a sum and a maximum, all ones for a
 //             minimum), unbinned, nan_rows <- 0 (one kernel, no memset node: see voxel_classes.hip's zero_kernel)
 //   rows      per row that takes part: one integer atomic add for the count and one 64-bit integer atomic per plane; a
@@ -31,6 +31,7 @@
 #include <cstring>
 #include "common.h"
 #include "binning.h"
+#include "packed_rows.h"
 #include "scan.h"
 
 namespace {
@@ -63,16 +64,6 @@ __device__ __forceinline__ void range_of(const Plan& plan, int p, const double* 
     const double hi = s < 3 ? d[3 + s] : plan.hi[p];
     lo = s < 3 ? d[s] : plan.lo[p];
     span = hi - lo;
-}
-
-// first tile whose rows can reach row `base`: the largest b with offsets[b] <= base (0 if there is none)
-__device__ __forceinline__ int tile_of(const int64_t* __restrict__ offsets, int B, int64_t base) {
-    int lo = 0, hi = B;   // first b in [0, B) with offsets[b] > base
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] > base) hi = mid; else lo = mid + 1;
-    }
-    return lo > 0 ? lo - 1 : 0;
 }
 
 // ---------------------------------------------------------------- clear
@@ -113,15 +104,10 @@ __global__ __launch_bounds__(kWaveLanes) void pool_rows_kernel(Plan plan, const 
     __shared__ double s_lo[kMaxP], s_inv[kMaxP];
     const int lane = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * kWaveChunk;
-    const int64_t end = base + kWaveChunk < total ? base + kWaveChunk : total;
     const int ne = nx + ny + nz + 3;
     const int64_t V = (int64_t)nx * ny * nz;
     const int P = plan.P, C = plan.C;
-    for (int b = tile_of(offsets, B, base); b < B; ++b) {
-        const int64_t lo = offsets[b], hi = offsets[b + 1];
-        if (lo >= end) break;
-        const int64_t from = lo > base ? lo : base, to = hi < end ? hi : end;
-        if (from >= to) continue;   // an empty tile, or one that ends before the chunk
+    sn::for_tiles(offsets, B, base, kWaveChunk, total, [&](int b, int64_t, int64_t, int64_t from, int64_t to) {
         const double* d = desc + (size_t)b * (size_t)(6 + ne);
         __syncthreads();   // the previous tile's table and quantisers have been read
         if (lane < P) {
@@ -185,7 +171,7 @@ __global__ __launch_bounds__(kWaveLanes) void pool_rows_kernel(Plan plan, const 
             if (nunb) __hip_atomic_fetch_add(unbinned + b, (unsigned long long)nunb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (nnan) __hip_atomic_fetch_add(nan_rows + b, (unsigned long long)nnan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    }
+    });
 }
 
 // ---------------------------------------------------------------- decode

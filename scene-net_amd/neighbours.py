@@ -87,6 +87,29 @@ def _grid(extent: Sequence[float], radius: float, B: int, max_cells: int):
     return dims, int(max(1, min(round(mult), 2 ** 62))) if math.isfinite(mult) else 2 ** 62
 
 
+def _tile_boxes(pts: torch.Tensor, offsets: torch.Tensor):
+    """The tiles' boxes from sn_voxel_bbox, an axis without finite coordinates [0, 0]: ONE read to the host"""
+    return [_usable_bounds(b) for b in _hip.voxel_bbox(pts, offsets).cpu().tolist()]
+
+
+def _tile_grid(pts: torch.Tensor, offsets: torch.Tensor, radius: float, lo, extent, max_cells: int, box=None):
+    """(lo [3 B] f64 on the device, dims, mult) of the tiles' search grids.  lo / extent None: from the tiles' boxes (`box`,
+    or ONE read to the host); both given, nothing is read."""
+    B = int(offsets.numel()) - 1
+    if lo is None or extent is None:
+        box = _tile_boxes(pts, offsets) if box is None else box
+        if extent is None:
+            extent = [max(b[3 + a] - b[a] for b in box) for a in range(3)]
+        if lo is None:
+            lo = torch.tensor([b[:3] for b in box], dtype=torch.float64, device=pts.device)
+    if not isinstance(lo, torch.Tensor) or not lo.is_cuda:
+        raise HipLibraryError("lo must live on a HIP device; there is no CPU path")
+    lo = lo.to(torch.float64).reshape(-1).contiguous()
+    if lo.numel() != 3 * B:
+        raise ValueError(f"lo must be [B, 3] = [{B}, 3]")
+    return (lo, *_grid(extent, radius, B, max_cells))
+
+
 def knn_distances(batch_or_xyz: Union[PointBatch, torch.Tensor], k: int, radius: Optional[float] = None,
                   exclude_zero: bool = False, want_index: bool = False, want_mean: bool = True, lo=None, extent=None,
                   max_cells: int = DEFAULT_MAX_CELLS, want_stats: Optional[bool] = None) -> PointNeighbours:
@@ -112,24 +135,14 @@ def knn_distances(batch_or_xyz: Union[PointBatch, torch.Tensor], k: int, radius:
     dev, total, B = pts.device, int(pts.shape[0]), int(offsets.numel()) - 1
     if total == 0 or B < 1:
         raise ValueError("knn_distances needs at least one point")
-    if (lo is None or extent is None) or radius is None:
-        box = _hip.voxel_bbox(pts, offsets).cpu().tolist()          # the one read
-        box = [_usable_bounds(b) for b in box]
-        if extent is None:
-            extent = [max(b[3 + a] - b[a] for b in box) for a in range(3)]
-        if lo is None:
-            lo = torch.tensor([b[:3] for b in box], dtype=torch.float64, device=dev)
-        if radius is None:
-            diag = max(math.sqrt(sum((b[3 + a] - b[a]) ** 2 for a in range(3))) for b in box)
-            radius = max(diag, 1e-9) * (1.0 + 1e-6)
-            extent = [0.0, 0.0, 0.0]                                # one cell per tile
-    if not isinstance(lo, torch.Tensor) or not lo.is_cuda:
-        raise HipLibraryError("lo must live on a HIP device; there is no CPU path")
-    lo = lo.to(torch.float64).reshape(-1).contiguous()
-    if lo.numel() != 3 * B:
-        raise ValueError(f"lo must be [B, 3] = [{B}, 3]")
+    box = None
+    if radius is None:
+        box = _tile_boxes(pts, offsets)                             # the one read
+        diag = max(math.sqrt(sum((b[3 + a] - b[a]) ** 2 for a in range(3))) for b in box)
+        radius = max(diag, 1e-9) * (1.0 + 1e-6)
+        extent = [0.0, 0.0, 0.0]                                    # one cell per tile
+    lo, dims, mult = _tile_grid(pts, offsets, radius, lo, extent, max_cells, box)
     radius = float(radius)
-    dims, mult = _grid(extent, radius, B, max_cells)
     ws = torch.empty(_hip.knn_ws_bytes(total, B, dims[0] * dims[1] * dims[2]) // 8, dtype=torch.int64, device=dev)
     d2 = torch.empty((total, k), dtype=torch.float64, device=dev)
     found = torch.empty((total,), dtype=torch.int32, device=dev)

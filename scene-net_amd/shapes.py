@@ -26,9 +26,8 @@ from typing import Optional, Sequence, Union
 import torch
 
 from . import _hip
-from ._hip import SN_SHAPE_NFEAT, HipLibraryError
-from .clusters import _usable_bounds
-from .neighbours import DEFAULT_MAX_CELLS, _as_batch, _grid
+from ._hip import SN_SHAPE_NFEAT
+from .neighbours import DEFAULT_MAX_CELLS, _as_batch, _tile_grid
 from .thin import ThinnedPoints, thin_points
 from .voxelization import PointBatch
 
@@ -92,19 +91,7 @@ def shape_features(batch_or_xyz: Union[PointBatch, torch.Tensor], radius: float,
     dev, total, B = pts.device, int(pts.shape[0]), int(offsets.numel()) - 1
     if total == 0 or B < 1:
         raise ValueError("shape_features needs at least one point")
-    if lo is None or extent is None:
-        box = _hip.voxel_bbox(pts, offsets).cpu().tolist()          # the one read
-        box = [_usable_bounds(b) for b in box]
-        if extent is None:
-            extent = [max(b[3 + a] - b[a] for b in box) for a in range(3)]
-        if lo is None:
-            lo = torch.tensor([b[:3] for b in box], dtype=torch.float64, device=dev)
-    if not isinstance(lo, torch.Tensor) or not lo.is_cuda:
-        raise HipLibraryError("lo must live on a HIP device; there is no CPU path")
-    lo = lo.to(torch.float64).reshape(-1).contiguous()
-    if lo.numel() != 3 * B:
-        raise ValueError(f"lo must be [B, 3] = [{B}, 3]")
-    dims, mult = _grid(extent, radius, B, max_cells)
+    lo, dims, mult = _tile_grid(pts, offsets, radius, lo, extent, max_cells)
     ws = torch.empty(_hip.shape_ws_bytes(total, B, dims[0] * dims[1] * dims[2]) // 8, dtype=torch.int64, device=dev)
     new = lambda cols, dtype=torch.float64: torch.empty((total, cols), dtype=dtype, device=dev)   # noqa: E731
     count = torch.empty((total,), dtype=torch.int32, device=dev)

@@ -27,7 +27,7 @@ import torch
 
 from . import _hip
 from ._hip import SN_THIN_GROUP_NONE, SN_THIN_GROUP_VOXEL, SN_THIN_GROUP_Z, HipLibraryError
-from .voxelization import PointBatch
+from .voxelization import PointBatch, _device_f64
 
 _GROUPS = {"none": SN_THIN_GROUP_NONE, "z": SN_THIN_GROUP_Z, "voxel": SN_THIN_GROUP_VOXEL}
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -86,14 +86,6 @@ class ThinnedPoints:
     first: Optional[torch.Tensor]
 
 
-def _device_f64(t, name: str) -> torch.Tensor:
-    if isinstance(t, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(torch.device("cuda", torch.cuda.current_device()))
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise HipLibraryError(f"{name} must live on a HIP device; there is no CPU path")
-    return t.to(torch.float64).contiguous()
-
-
 def _seed_tensor(seed, device) -> torch.Tensor:
     """[1] int64 on the device holding the u64's bit pattern."""
     if isinstance(seed, torch.Tensor):
@@ -127,11 +119,11 @@ def thin_points(batch: Union[PointBatch, torch.Tensor], thresholds=None, keep: O
             raise ValueError("labels come with the PointBatch")
         pb = batch
     else:
-        pts = _device_f64(batch, "batch")
+        pts = _device_f64(batch, "batch", numpy_ok=True)
         if pts.dim() != 2 or pts.shape[1] != 3:
             raise ValueError(f"xyz must be [n, 3] (got {tuple(pts.shape)})")
         n = int(pts.shape[0])
-        lab = None if labels is None else _device_f64(labels, "labels").reshape(-1)
+        lab = None if labels is None else _device_f64(labels, "labels", numpy_ok=True).reshape(-1)
         pb = PointBatch(pts, lab, torch.tensor([0, n], dtype=torch.int64, device=pts.device), (n,))
     if not pb.pts.is_cuda:
         raise HipLibraryError("the batch must live on a HIP device; there is no CPU path")
@@ -153,7 +145,7 @@ def thin_points(batch: Union[PointBatch, torch.Tensor], thresholds=None, keep: O
         if grids is None:
             desc, _ = _hip.voxel_prepare(pb.pts, pb.offsets, (nx, ny, nz), regular=True)
         else:
-            desc = _device_f64(getattr(grids, "desc", grids), "grids")
+            desc = _device_f64(getattr(grids, "desc", grids), "grids", numpy_ok=True)
     if thresholds is None:
         if keep is None:
             raise ValueError("one of thresholds and keep is needed")
@@ -165,7 +157,7 @@ def thin_points(batch: Union[PointBatch, torch.Tensor], thresholds=None, keep: O
                 raise ValueError("the height rule needs the z index: group 'z' or 'voxel'")
         else:
             thresholds = uniform_thresholds(float(keep), G)
-    thr = _device_f64(thresholds, "thresholds")
+    thr = _device_f64(thresholds, "thresholds", numpy_ok=True)
     if thr.numel() == G:
         thr = thr.reshape(1, G).expand(B, G).contiguous()
     if tuple(thr.shape) != (B, G):
@@ -173,7 +165,7 @@ def thin_points(batch: Union[PointBatch, torch.Tensor], thresholds=None, keep: O
     if u is not None and seed is not None:
         raise ValueError("u and seed are mutually exclusive")
     if u is not None:
-        u = _device_f64(u, "u").reshape(-1)
+        u = _device_f64(u, "u", numpy_ok=True).reshape(-1)
     else:
         seed = _seed_tensor(np.random.randint(0, 2 ** 63, dtype=np.int64) if seed is None else seed, dev)
     if tile_ids is None:
@@ -216,8 +208,8 @@ def thin_points(batch: Union[PointBatch, torch.Tensor], thresholds=None, keep: O
 def _mirror(xyz, classes, thresholds_of, group: str, seed, u):
     as_numpy = isinstance(xyz, np.ndarray)
     cls_dtype = classes.dtype
-    t = thin_points(_device_f64(xyz, "xyz"), keep=None, thresholds=thresholds_of(64), group=group, seed=seed, u=u,
-                    order="reference", want_src=False, labels=_device_f64(classes, "classes"))
+    t = thin_points(_device_f64(xyz, "xyz", numpy_ok=True), keep=None, thresholds=thresholds_of(64), group=group, seed=seed,
+                    u=u, order="reference", want_src=False, labels=_device_f64(classes, "classes", numpy_ok=True))
     pts, lab = t.batch.pts, t.batch.labels
     if as_numpy:
         return pts.cpu().numpy(), lab.cpu().numpy().astype(cls_dtype)

@@ -31,7 +31,7 @@ import torch
 
 from . import _hip
 from ._hip import HipLibraryError
-from .voxelization import PointBatch
+from .voxelization import PointBatch, _device_f64
 
 
 @dataclass
@@ -66,14 +66,6 @@ class ClassColors:
     short_table: torch.Tensor
 
 
-def _device_f64(t, name: str) -> torch.Tensor:
-    if isinstance(t, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(torch.device("cuda", torch.cuda.current_device()))
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise HipLibraryError(f"{name} must live on a HIP device; there is no CPU path")
-    return t.to(torch.float64).contiguous()
-
-
 def voxel_classes(batch: PointBatch, voxelgrid_dims: Sequence[int] = (64, 64, 64), desc: Optional[torch.Tensor] = None,
                   voxel_dims: Optional[Sequence[float]] = None) -> VoxelClasses:
     """classes_on_voxel for a whole batch: the largest label of every voxel of every tile (module docstring).
@@ -98,7 +90,7 @@ def voxel_classes(batch: PointBatch, voxelgrid_dims: Sequence[int] = (64, 64, 64
     if desc is not None:
         if voxel_dims is not None:
             raise ValueError("desc and voxel_dims are mutually exclusive")
-        desc = _device_f64(desc, "desc")
+        desc = _device_f64(desc, "desc", numpy_ok=True)
     elif voxel_dims is not None:
         bbox = _hip.voxel_bbox(batch.pts, batch.offsets)
         desc, dims, _ = _hip.voxel_desc_sized(bbox, voxel_dims, (nx, ny, nz))
@@ -127,12 +119,12 @@ def class_colors(classes, class_color, offsets: Optional[torch.Tensor] = None, l
       las          False: colors [total,3] f64.  True: rgb [total,3] uint16, what sna.write_las takes
       max_unique   columns of `unique` (default: the table's rows, where a table that serves reaches)
     Everything stays on the device; nothing is read back."""
-    cls = _device_f64(classes, "classes").reshape(-1)
+    cls = _device_f64(classes, "classes", numpy_ok=True).reshape(-1)
     dev = cls.device
     total = int(cls.numel())
     if total == 0:
         raise ValueError("class_colors needs at least one row")
-    table = _device_f64(class_color, "class_color")
+    table = _device_f64(class_color, "class_color", numpy_ok=True)
     if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1:
         raise ValueError(f"class_color must be [T, 3] with T >= 1 (got {tuple(table.shape)})")
     if offsets is None:
@@ -169,7 +161,7 @@ def color_pointcloud(pcd, classes, load: bool = False, pck_name: str = "class_co
         with open(pck_name, "rb") as handle:
             np_colors = pickle.load(handle)
     else:
-        cls = _device_f64(classes, "classes").reshape(-1)
+        cls = _device_f64(classes, "classes", numpy_ok=True).reshape(-1)
         dev = cls.device
         total = int(cls.numel())
         if total == 0:

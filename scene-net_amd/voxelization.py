@@ -81,6 +81,15 @@ class VoxelGrids:
     row_bits: Optional[torch.Tensor] = None  # [B,nz,ceil(nx/32)] i32, n-mode occupancy path: which (z, x) rows of occ hold a voxel
 
 
+def _device_f64(t, name: str, numpy_ok: bool = False) -> torch.Tensor:
+    """t as a contiguous f64 tensor on the device it lives on; with numpy_ok a host array is copied to the current one"""
+    if numpy_ok and isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(torch.device("cuda", torch.cuda.current_device()))
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _hip.HipLibraryError(f"{name} must live on a HIP device; there is no CPU path")
+    return t.to(torch.float64).contiguous()
+
+
 def _labels_list(tower_label) -> List[float]:
     return [float(v) for v in np.array(tower_label).reshape(-1)]
 

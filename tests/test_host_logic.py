@@ -429,3 +429,83 @@ def test_loss_plan_table_reaches_every_plan_class():
     need = {("one", True), ("one", False), ("several exact", True), ("several uneven", True), ("several uneven", False),
             ("capped exact", True), ("capped uneven", True), ("capped uneven", False)}
     assert reached["forward"] >= need and reached["backward"] >= need, reached
+
+
+def test_neighbourhood_workspace_sizes_are_pinned():
+    """sn_knn_ws_bytes and sn_shape_ws_bytes, recorded from the build before the sort's layout moved into cell_grid.h: the
+    statistics partials in front of K21's arrays, nothing in front of K22's, 0 for every shape that is not served."""
+    lib = _hip.load()
+    table = [  # total, B, cells per tile, knn, shape
+        (1, 1, 1, 160, 80),
+        (255, 1, 1, 9296, 9216),
+        (256, 1, 1, 9376, 9248),
+        (257, 3, 27, 10144, 9936),
+        (1000, 2, 64, 37280, 37040),
+        (12345, 7, 1001, 502736, 500496),
+        (100000, 8, 4096, 3878128, 3862160),
+        (1000, 1, 1 << 22, 33590656, 33590448),
+        (1000, 4096, 1024, 33754448, 33590448),
+        (1 << 30, 1, 1, 38822477936, 38654705696),
+        # the refusals: no rows, 2^31 rows, 2^30 + 1 rows (K22 only), one cell too many, no tiles, no cells
+        (0, 1, 1, 0, 0),
+        (-1, 1, 1, 0, 0),
+        ((1 << 31) - 1, 1, 1, 77644955696, 0),
+        (1 << 31, 1, 1, 0, 0),
+        ((1 << 30) + 1, 1, 1, 38822477984, 0),
+        (1000, 5, 838861, 0, 0),
+        (1000, 1, (1 << 22) + 1, 0, 0),
+        (1000, 0, 1, 0, 0),
+        (1000, 1, 0, 0, 0),
+    ]
+    assert 5 * 838861 == (1 << 22) + 1
+    for total, B, cells, knn, shape in table:
+        assert lib.sn_knn_ws_bytes(total, B, cells) == knn, (total, B, cells)
+        assert lib.sn_shape_ws_bytes(total, B, cells) == shape, (total, B, cells)
+
+
+def test_neighbourhood_grid_refusals_keep_their_words_and_their_order():
+    """The checks of radius, dims, mult and the cell budget that sn_knn_points and sn_shape_points share (cell_grid.h): code
+    and message, character for character, as both entries gave them when each spelled the checks out; and where two
+    arguments are wrong at once, the refusal that came first then comes first now."""
+    import ctypes
+    lib = _hip.load()
+    buf = ctypes.create_string_buffer(512)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) // 16 * 16)
+    big = ctypes.c_size_t(1 << 40)
+
+    def knn(total=100, B=2, radius=2.0, k=8, flags=0, dx=4, dy=4, dz=4, mult=1):
+        return lib.sn_knn_points(p, p, total, B, radius, k, flags, p, dx, dy, dz, mult, p, big, p, p, p, p, None)
+
+    def shape(total=100, B=2, radius=2.0, min_points=3, flags=0, dx=4, dy=4, dz=4, mult=1):
+        return lib.sn_shape_points(p, p, total, B, radius, min_points, flags, p, dx, dy, dz, mult, p, big, p, p, p, p, p, p, None)
+
+    shared = [  # arguments, code, message behind "<entry>: "
+        ({"radius": 0.0}, -1, "radius must be positive and finite"),
+        ({"radius": float("nan")}, -1, "radius must be positive and finite"),
+        ({"radius": float("inf")}, -1, "radius must be positive and finite"),
+        ({"dx": 0}, -1, "dims and mult must be at least 1 (got 0, 4, 4; 1)"),
+        ({"dz": -2, "mult": 0}, -1, "dims and mult must be at least 1 (got 4, 4, -2; 0)"),
+        ({"mult": -7}, -1, "dims and mult must be at least 1 (got 4, 4, 4; -7)"),
+        ({"dx": 1 << 11, "dy": 1 << 11, "dz": 2}, -2, "more than 2^22 cells (B * dims = 2 * 2048 * 2048 * 2)"),
+        ({"B": 3, "dx": 128, "dy": 128, "dz": 128}, -2, "more than 2^22 cells (B * dims = 3 * 128 * 128 * 128)"),
+        ({"radius": 1e-160}, -2, "radius beyond what is served (1e-150 .. 1e150)"),
+        ({"radius": 1e160}, -2, "radius beyond what is served (1e-150 .. 1e150)"),
+        # two at once: radius before dims, both before the flags, those before what is not served
+        ({"radius": -1.0, "dx": 0, "flags": 64}, -1, "radius must be positive and finite"),
+        ({"dy": 0, "flags": 64, "total": 1 << 31}, -1, "dims and mult must be at least 1 (got 4, 0, 4; 1)"),
+        ({"dx": 1 << 11, "dy": 1 << 11, "dz": 2, "radius": 1e160}, -2, "more than 2^22 cells (B * dims = 2 * 2048 * 2048 * 2)"),
+    ]
+    for call, who in ((knn, "sn_knn_points"), (shape, "sn_shape_points")):
+        for kw, code, text in shared:
+            assert call(**kw) == code, (who, kw)
+            assert lib.sn_last_error().decode() == f"{who}: {text}", (who, kw)
+    # each entry's own refusals keep their place between the two steps: flags in front of the cell budget, ...
+    assert knn(flags=2, dx=1 << 11, dy=1 << 11, dz=2) == -1 and lib.sn_last_error() == b"sn_knn_points: unknown flags 2"
+    assert shape(flags=2, dx=1 << 11, dy=1 << 11, dz=2) == -1
+    assert lib.sn_last_error() == b"sn_shape_points: unknown flags 2 (none are defined)"
+    # ... k and total in front of it too, behind the dims
+    assert knn(k=17, radius=1e160) == -2 and lib.sn_last_error() == b"sn_knn_points: k beyond what is served (at most 16, got 17)"
+    assert knn(total=1 << 31, radius=1e160) == -2 and lib.sn_last_error() == b"sn_knn_points: total < 2^31 rows are served"
+    assert shape(total=(1 << 30) + 1, radius=1e160) == -2
+    assert lib.sn_last_error() == b"sn_shape_points: total <= 2^30 rows are served (the moments stay inside int64)"
+    assert knn(k=17, dx=0) == -1 and shape(total=(1 << 30) + 1, mult=0) == -1
