@@ -141,6 +141,11 @@ int sn_device_count(void);
  *       launch a workgroup then checks its own jobs, fills those whose operand region holds no set voxel without walking them
  *       and walks the rest.  0 = two such segments on head-only launches with Z >= 32 and at least two columns in x that the
  *       dense plan would walk as whole columns, else that plan.  Same results bit for bit; ignored under "conv_i8z_dense".
+ *   "conv_i8z_trim" (switch, default 1): where the z-walk deals a tile's z segments by cost from the occupancy's row bits
+ *       (sn_conv_bank_prepared_rows), a live segment streams only the range from its first to its last output plane whose
+ *       operand window can hold a set voxel -- never fewer than min(8, segment) planes -- and the planes on either side are
+ *       filled with the epilogue's constant.  Same results bit for bit; 0 = every live segment is streamed whole (the A/B
+ *       switch).  No effect on any other launch.
  *   "conv_i8z_dense" (switch, default 0): the z-walk (sn_conv_bank_prepared[_served]) skips every round whose operand
  *       window -- 9 planes x 9 halo rows -- holds no set voxel and stores the epilogue's constant instead; the results are
  *       the same bit for bit (banks with a non-finite coefficient are never skipped), the run time depends on the data.
@@ -272,6 +277,11 @@ int sn_conv_i8_spin_timeouts(unsigned long long* count);
 /* Diagnostics: rounds the z-walk ran [0] and skipped because their operand window was empty [1] (see "conv_i8z_dense"), all
  * launches of this process on the device.  Each workgroup adds its sums once, at its end.  Synchronises the device. */
 int sn_conv_i8z_round_counts(unsigned long long* counts2);
+/* ... input planes the head-only z-walk streamed [0] and planes it did not stream because "conv_i8z_trim" cut them from a
+ * live segment [1], all launches since the library was loaded.  [0] counts EVERY head-only launch of the walk -- dense,
+ * static and dealt plans alike, whether or not anything can be trimmed; a z segment that is filled without being walked
+ * streams nothing and adds nothing.  Launches that write the per-kernel activations are not counted.  Synchronises. */
+int sn_conv_i8z_plane_counts(unsigned long long* counts2);
 /* Diagnostics: how many workgroups of the one-pass voxelisation kernel (sn_voxel_occupancy_fused[_bank] at grids whose bitmap
  * fits one workgroup) ever gave up the bounded wait of the box exchange and took their tile's box from the points themselves
  * -- the same bits, one more pass over the tile.  0 in normal use; every workgroup with option voxel_onepass_spin = 0.

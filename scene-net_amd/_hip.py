@@ -48,6 +48,7 @@ SYMBOLS = {
     "sn_conv_prep_verdict_offset": (c_int, []),
     "sn_conv_i8_spin_timeouts": (c_int, [_P]),
     "sn_conv_i8z_round_counts": (c_int, [_P]),
+    "sn_conv_i8z_plane_counts": (c_int, [_P]),
     "sn_voxel_onepass_giveups": (c_int, [_P]),
     "sn_launch_timing_events": (c_int, [_P, _P]),
     "sn_conv_fused": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
@@ -310,6 +311,15 @@ def conv_i8z_round_counts() -> Tuple[int, int]:
     that a workgroup filled without walking it (option conv_i8z_segments); synchronises (sn_conv_i8z_round_counts)."""
     buf = (ctypes.c_ulonglong * 2)()
     _check(load().sn_conv_i8z_round_counts(ctypes.cast(buf, ctypes.c_void_p)), "sn_conv_i8z_round_counts")
+    return int(buf[0]), int(buf[1])
+
+
+def conv_i8z_plane_counts() -> Tuple[int, int]:
+    """(planes streamed, planes trimmed away) by the head-only z-walk since the library was loaded, on the current device: where
+    the balanced deal stands a live z segment streams only its live output planes' range (option conv_i8z_trim), and the planes
+    it leaves out are counted in the second figure; synchronises (sn_conv_i8z_plane_counts)."""
+    buf = (ctypes.c_ulonglong * 2)()
+    _check(load().sn_conv_i8z_plane_counts(ctypes.cast(buf, ctypes.c_void_p)), "sn_conv_i8z_plane_counts")
     return int(buf[0]), int(buf[1])
 
 

@@ -42,6 +42,7 @@ Option g_options[] = {
     {"corr_sparse_tile_bytes", nullptr,                 0,  0,       0,  2048,    false},
     {"conv_i8z_inject_fault",  nullptr,                 0,  0,       0,  1,       true},
     {"conv_i8z_segments",      nullptr,                 0,  0,       0,  4,       false},
+    {"conv_i8z_trim",          nullptr,                 0,  1,       0,  1,       true},
     {"conv_i8z_dense",         nullptr,                 0,  0,       0,  1,       true},
 };
 static_assert(sizeof(g_options) / sizeof(g_options[0]) == kOptCount, "one entry per sn::Opt");

@@ -46,6 +46,7 @@ enum Opt {
     kOptCorrSparseTileBytes,
     kOptConvI8zInjectFault,
     kOptConvI8zSegments,
+    kOptConvI8zTrim,
     kOptConvI8zDense,
     kOptCount
 };

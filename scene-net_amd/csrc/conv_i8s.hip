@@ -360,6 +360,7 @@ int conv_occ_i8z(const uint8_t* x, const float* bank, const float* lambdas, uint
             z.deal_shift = z.nxt / n > 1 ? z.nxt / n : 1;
             z.fill_dead = act ? 0 : 1;
             if (z.fill_dead && bal_ok(n)) z.bal = 1;
+            if (z.bal && sn::option(sn::kOptConvI8zTrim)) z.trim = 1;   // (conv_i8z.inc, TRIMMED JOBS)
         }
     }
     if (z.bal) {
@@ -536,6 +537,15 @@ extern "C" int sn_conv_i8z_round_counts(unsigned long long* counts2) {
     unsigned long long h[2] = {0, 0};
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_zwalk_rounds), sizeof(h)) != hipSuccess)
         return sn::check_launch("sn_conv_i8z_round_counts");
+    counts2[0] = h[0]; counts2[1] = h[1];
+    return SN_OK;
+}
+
+extern "C" int sn_conv_i8z_plane_counts(unsigned long long* counts2) {
+    if (!counts2) return sn::fail(SN_ERR_INVALID_ARG, "sn_conv_i8z_plane_counts: null pointer");
+    unsigned long long h[2] = {0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_zwalk_planes), sizeof(h)) != hipSuccess)
+        return sn::check_launch("sn_conv_i8z_plane_counts");
     counts2[0] = h[0]; counts2[1] = h[1];
     return SN_OK;
 }

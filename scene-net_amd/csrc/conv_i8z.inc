@@ -35,7 +35,8 @@
 //
 // Ring arithmetic: plane u of the workgroup's plane stream (job k = u / PL, p = u % PL: grid plane zs_k - 4 + p) lives in
 // slot u & 15 of both rings.  Output o of job k needs planes k PL + o .. + 8; its four rounds ride on slot
-// k PL + o + kZD.  A fold pass at slot s overwrites plane s - 16, whose readers rode on slots s - 14 .. s - 6.
+// k PL + o + kZD.  A fold pass at slot s overwrites plane s - 16, whose readers rode on slots s - 14 .. s - 6.  (The head-only
+// form maps a stream position to its job with a cursor, and its jobs may differ in length: TRIMMED JOBS below.)
 //
 // EMPTY WINDOWS (round 6).  The input is LiDAR occupancy: a few per cent of the voxels are set, and a round whose operand
 // window -- 9 planes x 9 halo rows x the column's 96 halo bytes in y -- holds no set voxel has twelve accumulators that are
@@ -77,6 +78,19 @@
 // workgroup checks its own jobs in its prologue: one whose whole operand region holds no set voxel is not streamed at all -- its
 // outputs are filled with what its rounds would have stored and its rounds counted as skipped -- and the ticket loop walks the
 // live jobs only.  No extra launch, nothing shared between workgroups, nothing in the ticket loop: see DEAD JOBS in the kernel.
+//
+// TRIMMED JOBS (head-only form, where THE BALANCED DEAL stands; sn_set_option("conv_i8z_trim")).  A live job used to stream
+// LZ + 8 planes whatever it held; a plane costs its four tickets (claim, dependency check, LDS-DMA, fold pass).  Output plane z
+// of a job is LIVE when the nine-plane window W[z] of the tile's row bits has a bit in rows x0 - 4 .. x0 + 11; a plane that is
+// not has every round empty under EMPTY WINDOWS' rule.  After the deal -- which does not change: same costs, same tables -- a
+// live job is cut to [a, a + len): from its first to its last live output plane, never below min(8, LZ) outputs (the shortest
+// uniform job the launch rules allow: 16 planes, one ring's worth), padded upwards, and downwards where the segment ends first.
+// Job k of the workgroup's live jobs occupies stream positions [S_k, S_k + len_k + 8); its output o is grid plane a_k + o, its
+// plane p grid plane a_k - 4 + p.  The hand-over protocol lives in stream coordinates and is untouched: only the map from a
+// stream position to (job, plane) changes, from a division by PL to a CURSOR (a wave's positions only grow: it keeps its job's
+// stream end and steps to the next job when a position reaches it -- one LDS read when the job changes, none otherwise).  The
+// flanks [z0, a) and [a + len, z1) are filled in the prologue with the dead jobs, their rounds counted as skipped.
+// sn_conv_i8z_plane_counts: planes streamed / trimmed away (head-only form), per workgroup in LDS, added once at its end.
 
 constexpr int kZTX = 8;                        // output x-rows per column
 constexpr int kZRows = kZTX + 8;               // halo rows per plane
@@ -143,12 +157,16 @@ struct ZShape {
     int deal, deal_shift;         // jobs in segment-major order, segment sg of column (b, yt, xt) dealt as column xt + shift sg
                                   // (mod nxt): a workgroup's segments come from different columns (SN_I8Z_SKIP_NSEG)
     int bal;                      // THE BALANCED DEAL: the workgroups of a tile share its jobs by cost, from `rows`
+    int trim;                     // TRIMMED JOBS (bal only; sn_set_option("conv_i8z_trim")): a live job streams its live output
+                                  // planes only
     const uint32_t* rows;         // the occupancy's row bits [B][Z][ceil(X / 32)] (sn_conv_bank_prepared_rows), bal only
     int32_t* plan_out;            // nullable, bal only: row blockIdx.x of [grid][1 + kZBalJobs] = (count, job numbers ...)
 };
 
 // diagnostics (sn_conv_i8z_round_counts): rounds the walk ran / skipped (empty operand window), all launches since load
 __device__ unsigned long long g_zwalk_rounds[2] = {0ull, 0ull};
+// ... (sn_conv_i8z_plane_counts): planes the head-only walk streamed / did not stream because TRIMMED JOBS cut them away
+__device__ unsigned long long g_zwalk_planes[2] = {0ull, 0ull};
 
 __device__ __forceinline__ int zjob_id(const ZShape& z, int wg, int k, int grid) {
     const int base = k * grid;
@@ -401,7 +419,9 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // LDS carve-up
     uint4* Wd = reinterpret_cast<uint4*>(lds);                                   // [4][3][64] x 16 B
-    int4* jobtab = reinterpret_cast<int4*>(Wd + kFoldSteps * 3 * 64);            // [kZMaxJobs] (b, x0, y0, zs)
+    int4* jobtab = reinterpret_cast<int4*>(Wd + kFoldSteps * 3 * 64);            // [kZMaxJobs] (b, x0, y0, zs); THE BALANCED DEAL's
+                                                                                 // table (one y tile: y0 = 0) holds a | len << 8 of
+                                                                                 // TRIMMED JOBS in the y0 field
     float* scale = reinterpret_cast<float*>(jobtab + kZMaxJobs);                 // [16]
     float* lamsc = scale + 16;                                                   // [16]
     float* lamhi = lamsc + 16;                                                   // [16] (+ 64 bytes spare)
@@ -421,6 +441,8 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     //           [32..95] landed[pass][slot]: LDS-DMA passes arrived;  [96] ticket counter;  [97] asymmetric bank;  [98] a spin gave up
     //           [99] can_skip;  [100] rounds run, [101] rounds skipped, [102] waves that have added theirs;  [103] live jobs (DEAD JOBS;
     //           THE BALANCED DEAL: the live jobs of this workgroup's share);  [104] THE BALANCED DEAL: jobs in this workgroup's table.
+    //           [105] TRIMMED JOBS: planes of the workgroup's stream (the sum of len + 8 over its live jobs);  [106], [107] planes
+    //           streamed / trimmed away, for the device's count.
     //           [103] / [104] are written by wave 0 ahead of the prologue's second barrier and, when the launch may not skip, once
     //           more by wave 0 behind the verdict (the static table and its count).  `dealt` -- which poison_jobs walks -- is read
     //           from [104] right behind the second barrier and again behind the __syncthreads that ends the prologue.  A slow
@@ -538,6 +560,29 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         return true;
     };
     JobRegs jd{-1, 0, 0, 0, 0}, jr{-1, 0, 0, 0, 0};
+    // kLean, THE CURSOR (TRIMMED JOBS): a job's stream positions [s0, end) and its outputs `len` ride beside its registers, and
+    // `zs` is the grid plane of its output 0 (a trimmed job: a, else the segment's first plane).  A wave's stream positions only
+    // grow -- the prologue's planes in order, then sd = s + kZDD of ever later tickets; sigma likewise -- so it steps to the next
+    // job while the position is at or past `end`: one LDS read when the job changes, none otherwise.  Every position asked for
+    // lies below NPL, i.e. inside a live job of the table.
+    bool bal_keep = false;   // THE BALANCED DEAL's table stands (the launch may skip): its y0 fields hold a | len << 8
+    struct JobSpan { int next, s0, end, len; };
+    JobSpan sd_{0, 0, 0, 0}, sr_{0, 0, 0, 0};
+    auto job_step = [&](JobRegs& j, JobSpan& sp) {
+        const int4 jb = jobtab[sp.next & (kZMaxJobs - 1)];   // (the mask: a table address with an immediate offset)
+        int a = jb.w, len = zs.LZ, y0 = jb.z;
+        if (bal_keep) {
+            a = jb.z & 255;
+            len = jb.z >> 8;
+            y0 = 0;
+        }
+        j.b = __builtin_amdgcn_readfirstlane(jb.x); j.x0 = __builtin_amdgcn_readfirstlane(jb.y);
+        j.y0 = __builtin_amdgcn_readfirstlane(y0); j.zs = __builtin_amdgcn_readfirstlane(a);
+        j.k = sp.next++;
+        sp.len = __builtin_amdgcn_readfirstlane(len);
+        sp.s0 = sp.end;
+        sp.end = sp.s0 + sp.len + 8;
+    };
     // kLean: the jobs' tile bases x + b V and out + b V are 64-bit scalars formed when the job changes, not per pass and per
     // round (round 7: the product b V was formed three times per ticket); everything below adds 32-bit offsets (the host
     // checks Z X Y < 2^31)
@@ -547,10 +592,17 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     // ---- LDS-DMA of four raw rows (pass xr) of plane u: 24 lanes x 16 B, rows contiguous in the ring slot
     auto dma_pass = [&](int u, int xr, int ln) {
         const int dl_row = (ln * 43) >> 8, dl_i = ln - dl_row * kRowPieces;   // ln / 6, ln % 6 for ln < 24 (the lanes that take part)
-        const int k = (int)__umulhi((unsigned)u, zs.pl_magic), p = u - k * zs.PL;
-        const bool new_job = job_fetch(jd, k);
+        int p;
         if constexpr (kLean) {
-            if (new_job) xb = x + (size_t)jd.b * V;
+            while (u >= sd_.end && sd_.next < dealt) {   // (the bound cannot bind: u < NPL; it keeps a wrong table from spinning)
+                job_step(jd, sd_);
+                xb = x + (size_t)jd.b * V;
+            }
+            p = u - sd_.s0;
+        } else {
+            const int k = (int)__umulhi((unsigned)u, zs.pl_magic);
+            p = u - k * zs.PL;
+            job_fetch(jd, k);
         }
         const int gz = jd.zs - 4 + p;
         const int gx = jd.x0 - 4 + 4 * xr + dl_row, gy = jd.y0 - PYA + 16 * dl_i;
@@ -594,7 +646,8 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
     auto poison_jobs = [&]() {
         const OT nan = (OT)__int_as_float(0x7fc00000);
         for (int k = 0; k < dealt; ++k) {   // (every job the workgroup was dealt: walked or filled)
-            const int4 jb = jobtab[k];
+            int4 jb = jobtab[k];
+            if (bal) jb.z = 0;   // (THE BALANCED DEAL: one y tile, and its table's y0 fields hold TRIMMED JOBS' ranges)
             for (int r = wave; r < zs.LZ * kZTX; r += kW) {
                 const int gz = jb.w + (r >> 3), gx = jb.y + (r & 7), gy = jb.z + lane;
                 if (gz >= zs.Z || gx >= zs.X || gy >= zs.Y) continue;
@@ -700,6 +753,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
                                      zreg = zbits(z0 - 4 > 0 ? (z0 - 4 < 64 ? z0 - 4 : 64) : 0, z1 + 4 < zs.Z ? z1 + 4 : zs.Z);
             bool lv = false;
             int rounds = 0;
+            unsigned long long lvw = 0ull;   // TRIMMED JOBS: this job's live output planes
 #pragma unroll 1
             for (int xt = 0; xt < nxt; ++xt) {
                 const int x0 = xt * kZTX;
@@ -709,6 +763,9 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
                 const bool is_mine = xt == xt_mine;
                 const unsigned long long lb = __builtin_amdgcn_ballot_w64(raw16 != 0u);
                 if (is_mine) lv = (lb & zreg) != 0ull;
+                // (the OR over h of the rounds' ballots below: a plane with no bit here has every round empty, for either kH)
+                const unsigned long long wl = __builtin_amdgcn_ballot_w64(win16 != 0u);
+                if (is_mine) lvw = wl & zrun;
                 const int nrows = zs.X - x0 < kZTX ? zs.X - x0 : kZTX;
 #pragma unroll
                 for (int h = 0; h < kZTX; h += kH) {
@@ -750,10 +807,24 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             const unsigned long long lvb = __builtin_amdgcn_ballot_w64(mine && (sk >> 6) > (uint32_t)kBalFill);
             const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
             const int n_mine = __builtin_popcountll(mb);
+            // TRIMMED JOBS: this lane's job streams outputs [ta, ta + tlen) -- from its first to its last live plane, at least
+            // min(8, LZ) of them, moved down where the segment ends first; the whole segment without the option (or should the
+            // two verdicts ever disagree: lv is the one the deal and the fill go by).  Lane s fetches its job's pair from lane jj.
+            int ta = z0, tlen = zs.LZ;
+            if (zs.trim && lvw != 0ull) {
+                const int lmin = zs.LZ < 8 ? zs.LZ : 8;
+                ta = __builtin_ctzll(lvw);
+                tlen = 64 - __builtin_clzll(lvw) - ta;
+                tlen = tlen < lmin ? lmin : tlen;
+                if (ta + tlen > z1) ta = z1 - tlen;
+            }
+            const int tr = __shfl(ta | (tlen << 8), lane < nj ? 63 - (int)(sk & 63u) : 0, 64);
+            const bool mine_live = mine && (sk >> 6) > (uint32_t)kBalFill;
+            if (mine_live) atomicAdd(&cnt[105], (tr >> 8) + 8);   // (few lanes, once per launch)
             if (mine) {
                 const int jj = 63 - (int)(sk & 63u);
                 const int jsg = jj / nxt, jxs = jj - jsg * nxt;
-                jobtab[pos] = make_int4(b, ((jxs + zs.deal_shift * jsg) % nxt) * kZTX, 0, jsg * zs.LZ);
+                jobtab[pos] = make_int4(b, ((jxs + zs.deal_shift * jsg) % nxt) * kZTX, tr, jsg * zs.LZ);   // (y0 = 0: tr in its field)
                 if (zs.plan_out) zs.plan_out[(size_t)blockIdx.x * (1 + kZBalJobs) + 1 + pos] = jsg * (zs.B * nxt) + b * nxt + jxs;
             }
             if (lane == 0) {
@@ -804,13 +875,16 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         }
         return __builtin_amdgcn_ballot_w64(!fin) == 0ull;
     };
-    bool bal_keep = false;   // the balanced table stands (the launch may skip)
     if constexpr (kLean) {
         if (bal) {
             // the balanced table's first job, if live, stays the first whatever the verdict says -- unless the launch may not
             // skip (wave 0 then restores the static table, below): every wave looks at the coefficients itself
             dealt = __builtin_amdgcn_readfirstlane(cnt[104]);
             bal_keep = coef_finite() && !zs.dense;
+            // (TRIMMED JOBS: the first live job's own plane count, len_0 + 8, is what must cover the prologue's kZPre planes.
+            // len_0 >= min(8, LZ), so with kZPre <= 16 -- asserted here -- len_0 + 8 >= kZPre exactly when PL = LZ + 8 >= kZPre:
+            // LZ >= 8 gives len_0 + 8 >= 16; LZ < 8 gives len_0 = LZ.  The uniform test therefore IS the job's own.)
+            static_assert(kZPre <= 16, "a trimmed job of min(8, LZ) + 8 planes covers the prologue's planes whenever PL does");
             if (bal_keep && zs.PL >= kZPre && __builtin_amdgcn_readfirstlane(cnt[103]) > 0) {
                 early = true;
                 for (int p = wave; p < 4 * npre; p += kW) dma_pass(p >> 2, p & 3, lane);
@@ -916,7 +990,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             // DEAD JOBS: the stream is the live jobs'.  Unless they are in flight already, its first planes are requested now,
             // and the dead jobs are filled while they fly.
             my_jobs = __builtin_amdgcn_readfirstlane(cnt[103]);
-            NPL = my_jobs * zs.PL;
+            NPL = bal_keep ? __builtin_amdgcn_readfirstlane(cnt[105]) : my_jobs * zs.PL;   // (TRIMMED JOBS: the sum of len + 8)
             nslots = NPL + kZD;
             if (!early) {
                 npre = NPL < kZPre ? NPL : kZPre;
@@ -926,10 +1000,23 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             // what a dead job's rounds would have stored, four values per thread and store: zero_round1 / zero_round2's
             // operations from e = + 0.0 on (the zero made opaque so that they are issued), for the rows and planes inside the grid
             int dead_rounds = 0;
+            // (TRIMMED JOBS: the ranges are the dead jobs' whole segments and, under bal_keep, the two flanks [z0, a) and
+            // [a + len, z1) of every live job -- item 2 k and 2 k + 1; an untrimmed job's flanks are empty)
+            const int nflank = bal_keep ? 2 * my_jobs : 0;
 #pragma unroll 1
-            for (int k = my_jobs; k < dealt; ++k) {
-                const int4 jb = jobtab[k];
-                const int nz = zs.Z - jb.w < zs.LZ ? zs.Z - jb.w : zs.LZ;
+            for (int it = 0; it < nflank + dealt - my_jobs; ++it) {
+                const bool flank = it < nflank;
+                const int k = flank ? it >> 1 : my_jobs + it - nflank;
+                int4 jb = jobtab[k];
+                int nz = zs.Z - jb.w < zs.LZ ? zs.Z - jb.w : zs.LZ;
+                const int t = jb.z;
+                if (bal) jb.z = 0;   // (one y tile; the field holds a | len << 8)
+                if (flank) {
+                    const int a = t & 255, e = a + (t >> 8);
+                    if (it & 1) { nz = jb.w + nz - e; jb.w = e; }
+                    else nz = a - jb.w;
+                    if (nz <= 0) continue;
+                }
                 const int nx = zs.X - jb.y < kZTX ? zs.X - jb.y : kZTX;
                 const int ny4 = (zs.Y - jb.z < TY ? zs.Y - jb.z : TY) >> 2;
                 dead_rounds += nz * ((nx + kH - 1) / kH);
@@ -976,6 +1063,12 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             }
         }
     }
+    if constexpr (kLean) {
+        if (tid == 0) {   // (for the device's plane counts, added with the round counts at the workgroup's end)
+            cnt[106] = NPL;
+            cnt[107] = my_jobs * zs.PL - NPL;
+        }
+    }
     SN_ST(4);
 
     bool healthy = true;
@@ -1019,9 +1112,19 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
         int kr = 0, o = 0;
         bool has_round = false;
         if (sigma >= 0) {
-            kr = (int)__umulhi((unsigned)sigma, zs.pl_magic);
-            o = sigma - kr * zs.PL;
-            has_round = o < zs.LZ;
+            if constexpr (kLean) {
+                // THE CURSOR: sigma < NPL (nslots = NPL + kZD), so the job it reaches is one of the table's live ones
+                while (sigma >= sr_.end && sr_.next < dealt) {
+                    job_step(jr, sr_);
+                    if (out) ob = out + (size_t)jr.b * V;
+                }
+                o = sigma - sr_.s0;
+                has_round = o < sr_.len;
+            } else {
+                kr = (int)__umulhi((unsigned)sigma, zs.pl_magic);
+                o = sigma - kr * zs.PL;
+                has_round = o < zs.LZ;
+            }
         }
         // a pass this wave requested in an earlier ticket and has not reported yet (that ticket had no round to hide the
         // wait behind).  Reported before anything is waited for: this ticket's own dependencies may lead back to it
@@ -1103,10 +1206,7 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             continue;
         }
         const unsigned long long tz3 = SN_ZNOW();
-        const bool new_job = job_fetch(jr, kr);
-        if constexpr (kLean) {
-            if (new_job && out) ob = out + (size_t)jr.b * V;
-        }
+        if constexpr (!kLean) job_fetch(jr, kr);   // (kLean: the cursor above)
         const int gz = jr.zs + o;
         const int lx = kH * kR * tk;   // the ticket's first x-row
         int rows_left = 0, nvalid = 0;   // rounds of this ticket that lie inside the grid (x-rows past X end the ticket early)
@@ -1426,6 +1526,10 @@ __global__ __launch_bounds__(64 * kW) void conv_occ_i8z_kernel(const uint8_t* __
             const volatile __attribute__((address_space(3))) int* tot = (__attribute__((address_space(3))) int*)cnt;
             atomicAdd(&g_zwalk_rounds[0], (unsigned long long)(unsigned)tot[100]);
             atomicAdd(&g_zwalk_rounds[1], (unsigned long long)(unsigned)tot[101]);
+            if constexpr (kLean) {
+                atomicAdd(&g_zwalk_planes[0], (unsigned long long)(unsigned)tot[106]);
+                atomicAdd(&g_zwalk_planes[1], (unsigned long long)(unsigned)tot[107]);
+            }
         }
     }
     // ---- a wave of this workgroup gave up: nothing the workgroup wrote can be trusted.  Every wave that is still alive gets

@@ -8,7 +8,10 @@ rounds in ONE process on the bench's C2 batch (cdna_hip_programming.md rule 24).
                                         skips every round), with the rounds run / skipped of one launch
     python tools/conv_ab.py --skip --bits   the same three inputs through sn_conv_bank_prepared_rows: without row bits (the
                                         static two-segment deal and its byte check), with bits and two segments, with bits
-                                        and four (the default with bits at Z = 64): the balanced deal, conv_i8z.inc"""
+                                        and four (the default with bits at Z = 64): the balanced deal, conv_i8z.inc
+    python tools/conv_ab.py --skip --bits --trim   ... and the two rows with bits once more under conv_i8z_trim = 0 (every live
+                                        job streamed whole), with the planes one launch streamed / trimmed away: on random
+                                        50 % and on all zero nothing can be trimmed -- those pairs price the cursor"""
 import argparse
 import os
 import sys
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--random-occ", type=float, default=0.0, help="random occupancy of this density instead of tiles")
     ap.add_argument("--skip", action="store_true", help="dense / skip rows of the z-walk on three inputs")
     ap.add_argument("--bits", action="store_true", help="with --skip: hand the occupancy's row bits to the walk")
+    ap.add_argument("--trim", action="store_true", help="with --skip --bits: rows under conv_i8z_trim = 0 beside the default")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     specs, names, lambdas, last = synthetic_bank_spec()
@@ -170,11 +174,14 @@ def bits_ab(args, tiles_occ, bank, lam, prep):
     B, _, Z, X, Y = tiles_occ.shape
     G = bank.shape[0]
     stream = torch.cuda.current_stream().cuda_stream
-    modes = {"no bits": (False, 0), "bits, 2 segments": (True, 2), "bits, 4 segments": (True, 4)}
+    modes = {"no bits": (False, 0, 1), "bits, 2 segments": (True, 2, 1), "bits, 4 segments": (True, 4, 1)}
+    if args.trim:
+        modes.update({"bits, 2, untrimmed": (True, 2, 0), "bits, 4, untrimmed": (True, 4, 0)})
 
     def run(name, mode, n):
-        with_bits, seg = modes[mode]
+        with_bits, seg, trim = modes[mode]
         _hip.set_option("conv_i8z_segments", seg)
+        _hip.set_option("conv_i8z_trim", trim)
         for _ in range(n):
             rc = fn(inputs[name].data_ptr(), _hip.SN_OCC8, bank.data_ptr(), lam.data_ptr(), prep.data_ptr(), B, Z, X, Y, G, 9, 9,
                     9, None, out.data_ptr(), _hip.SN_F32, stream, 1, bits[name].data_ptr() if with_bits else None, None)
@@ -182,7 +189,7 @@ def bits_ab(args, tiles_occ, bank, lam, prep):
 
     rows = [(name, mode) for name in inputs for mode in modes]
     res = {r: [] for r in rows}
-    kept = {}
+    kept, planes = {}, {}
     t_spin = time.perf_counter()
     while time.perf_counter() - t_spin < 0.3:
         run("C2 batch", "no bits", 10)
@@ -192,6 +199,10 @@ def bits_ab(args, tiles_occ, bank, lam, prep):
             run(name, mode, 5)
             torch.cuda.synchronize()
             if r == 0:
+                p0 = _hip.conv_i8z_plane_counts()
+                run(name, mode, 1)
+                p1 = _hip.conv_i8z_plane_counts()
+                planes[(name, mode)] = (p1[0] - p0[0], p1[1] - p0[1])
                 kept[(name, mode)] = out.clone()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -200,11 +211,12 @@ def bits_ab(args, tiles_occ, bank, lam, prep):
             torch.cuda.synchronize()
             res[(name, mode)].append(e0.elapsed_time(e1) / args.iters)
     _hip.set_option("conv_i8z_segments", 0)
+    _hip.set_option("conv_i8z_trim", 1)
     for name, mode in rows:
         ts = res[(name, mode)]
         same = torch.equal(kept[(name, mode)].view(torch.int32), kept[(name, "no bits")].view(torch.int32))
-        print(f"{name:12s} {mode:17s} median {float(np.median(ts)) * 1e3:8.1f} us  min {float(np.min(ts)) * 1e3:8.1f} us  "
-              f"same bits {same}  rounds {[round(t * 1e3, 1) for t in ts]}")
+        print(f"{name:12s} {mode:18s} median {float(np.median(ts)) * 1e3:8.1f} us  min {float(np.min(ts)) * 1e3:8.1f} us  "
+              f"same bits {same}  planes streamed {planes[(name, mode)][0]} trimmed {planes[(name, mode)][1]}  rounds {[round(t * 1e3, 1) for t in ts]}")
     print(f"spin give-ups {_hip.conv_i8_spin_timeouts()}, device status {_hip.device_status()[0]}")
 
 

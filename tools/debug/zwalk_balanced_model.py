@@ -25,6 +25,13 @@ ties to the lowest.  A workgroup's table is its jobs in that order (the live one
   plan(B, Z, X, Y, segments, bits=True, ...)   -> zwalk_plan_model.plan + "bal"
   deal(rows, p, kH)              -> per workgroup: list of job numbers, and the number of live ones
   cost_us(rows, p, kH)           -> modelled microseconds per workgroup (the plan model's constants)
+
+TRIMMED JOBS (option conv_i8z_trim): after the deal, which does not change, a live job streams only the range from its first
+to its last live output plane (live_planes), never fewer than min(8, LZ) outputs; its flanks are filled like dead jobs.
+  live_range(rowsb, p, job)      -> (a, len) or None for a dead job
+  trimmed_stream(rows, p, kH)    -> per workgroup: [(job number, a, len, S)] and the planes of its stream
+  plane_counts(rows, p, kH)      -> (planes streamed, planes trimmed away), as sn_conv_i8z_plane_counts counts them
+  cost_us_trimmed(rows, p, kH)   -> cost_us with the trimmed streams
   python tools/debug/zwalk_balanced_model.py   the benchmark's batch: static and balanced plans, max / median / mean"""
 import os
 import sys
@@ -141,6 +148,64 @@ def cost_us(rows, p, kH=1):
     return np.array(t)
 
 
+def live_planes(rowsb, p, job):
+    """output planes of the job's segment that are LIVE: W[z] -- the OR of the row booleans over planes z - 4 .. z + 4 -- has
+    a bit in rows x0 - 4 .. x0 + 11 (clipped).  A plane that is not live has every round empty, for either kH."""
+    b, x0, _, zs = job
+    Z, X, LZ = p["Z"], p["X"], p["LZ"]
+    return [z for z in range(zs, min(Z, zs + LZ))
+            if rowsb[b, max(0, z - 4):min(Z, z + 5), max(0, x0 - 4):min(X, x0 + 12)].any()]
+
+
+def live_range(rowsb, p, job):
+    """TRIMMED JOBS (csrc/conv_i8z.inc): (a, len) of a live job -- outputs a .. a + len - 1, from its first to its last live
+    plane, at least Lmin = min(8, LZ) of them, extended upwards and moved down where the segment ends first -- or None for a
+    dead job (no live plane: the same verdict as job_cost's `live`)."""
+    _, _, _, zs = job
+    z1 = min(p["Z"], zs + p["LZ"])
+    m = live_planes(rowsb, p, job)
+    if not m:
+        return None
+    a, n = m[0], max(m[-1] + 1 - m[0], min(8, p["LZ"]))
+    n = min(n, z1 - zs)                 # (a last segment shorter than Lmin: outside the balanced deal's guard)
+    if a + n > z1:
+        a = z1 - n
+    return a, n
+
+
+def trimmed_stream(rows, p, kH=1, trim=True):
+    """per workgroup, under the UNCHANGED deal: [(job number, a, len, S)] of its live jobs in table order -- job k occupies
+    stream positions S .. S + len + 8 -- and the planes of its stream.  trim=False: whole segments."""
+    rowsb = rows_to_bool(rows, p["X"])
+    out = []
+    for js, nlive in deal(rows, p, kH):
+        S, mine = 0, []
+        for j in js[:nlive]:
+            job = pm.decode(p, j)[0]
+            a, n = live_range(rowsb, p, job) if trim else (job[3], min(p["LZ"], p["Z"] - job[3]))
+            mine.append((j, a, n, S))
+            S += n + 8
+        out.append((mine, S))
+    return out
+
+
+def plane_counts(rows, p, kH=1, trim=True):
+    """(planes streamed, planes trimmed away) of one launch: what sn_conv_i8z_plane_counts adds"""
+    st = trimmed_stream(rows, p, kH, trim)
+    streamed = sum(S for _, S in st)
+    return streamed, sum(len(m) for m, _ in st) * p["PL"] - streamed
+
+
+def cost_us_trimmed(rows, p, kH=1):
+    """cost_us with every live job cut to its live range: the same deal, the same rounds run, fewer planes"""
+    rowsb = rows_to_bool(rows, p["X"])
+    t = []
+    for mine, planes in trimmed_stream(rows, p, kH):
+        rounds = sum(job_cost(rowsb, p, pm.decode(p, j)[0], kH)[2] for j, _, _, _ in mine)
+        t.append(pm.T_PROLOGUE + pm.T_PLANE * planes + pm.T_ROUND * rounds)
+    return np.array(t)
+
+
 def bench_occ():
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     sys.path.insert(0, root)
@@ -163,6 +228,10 @@ def main():
         dead = sum(not job_cost(rows_to_bool(rows, 64), p, pm.decode(p, j)[0], 1)[1] for j in range(p["njobs"]))
         print(f"{name}: {p['njobs']} jobs, {dead} dead, bal {p['bal']}; workgroup us max {t.max():.1f} "
               f"median {np.median(t):.1f} mean {t.mean():.1f}")
+        if p["bal"]:
+            tt = cost_us_trimmed(rows, p, 1)
+            print(f"    trimmed to the live ranges, same deal: planes {plane_counts(rows, p, 1, trim=False)[0]} -> "
+                  f"{plane_counts(rows, p, 1)[0]}; workgroup us max {tt.max():.1f} median {np.median(tt):.1f} mean {tt.mean():.1f}")
 
 
 if __name__ == "__main__":

@@ -39,15 +39,22 @@ class Hazard(Exception):
 
 
 def simulate(my_jobs, LZ, kTPS, nwaves, seed, lag=3, dd=4, ordered_reads=True, skip_prob=0.0, adversarial=True,
-             max_steps=2_000_000, freeze_slot=None):
+             max_steps=2_000_000, freeze_slot=None, lens=None):
     """kTPS tickets per slot: 8 (one round of one x-row per ticket; even tickets carry a pass), 4 (two rounds; every ticket
-    one pass: the shipped shape), 2 (four rounds, two passes)."""
-    PL = LZ + 8
+    one pass: the shipped shape), 2 (four rounds, two passes).
+    lens: TRIMMED JOBS -- the jobs' output counts, one per job (my_jobs and LZ are then ignored): job k occupies the stream
+    positions S_k .. S_k + lens[k] + 7, and a position carries a round iff it is one of the first lens[k] of its job."""
+    if lens is None:
+        lens = [LZ] * my_jobs
+    round_at = []                     # stream position -> it carries a round (the kernel's cursor: o < len_k)
+    for n in lens:
+        assert n >= 1
+        round_at += [True] * n + [False] * 8
     kZD = 8 + lag
     kPre = kZD + dd
     assert kPre <= RING and RING - 8 - lag >= 2
     kPPT = 2 if kTPS == 2 else 1
-    NPL = my_jobs * PL
+    NPL = len(round_at)
     nslots = NPL + kZD
     ntickets = kTPS * nslots
     npre = min(NPL, kPre)
@@ -74,8 +81,7 @@ def simulate(my_jobs, LZ, kTPS, nwaves, seed, lag=3, dd=4, ordered_reads=True, s
         sigma = s - kZD
         has_round = False
         if sigma >= 0:
-            _, o = divmod(sigma, PL)
-            has_round = o < LZ
+            has_round = round_at[sigma]
         return s, tk, xr0, sd, sigma, has_dma, has_fold, has_round
 
     def deps_ok(t):
@@ -213,6 +219,9 @@ def simulate(my_jobs, LZ, kTPS, nwaves, seed, lag=3, dd=4, ordered_reads=True, s
 
 
 SHAPES = [(1, 1), (1, 3), (1, 8), (1, 20), (1, 64), (2, 8), (2, 26), (3, 5), (5, 1), (4, 32), (1, 128)]
+# TRIMMED JOBS: streams of jobs of different lengths, the shortest the kernel forms (8 outputs, 16 planes) included; the last
+# two hold jobs the kernel never forms under the balanced deal's guard (below 8 outputs), for the protocol's sake
+MIXED = [[8, 16], [16, 8], [8, 8, 8], [9, 16, 8, 13], [16, 8, 16, 8, 11], [8, 15, 8, 10, 16, 8, 9, 12], [1, 16, 3, 8], [5, 1, 8]]
 
 
 def run_all(ordered_reads, seeds=range(8), verbose=True):
@@ -226,6 +235,15 @@ def run_all(ordered_reads, seeds=range(8), verbose=True):
                             simulate(my_jobs, LZ, kTPS, nw, seed, ordered_reads=ordered_reads, skip_prob=skip, adversarial=adversarial)
                         except Hazard as e:
                             bad.append((kTPS, nw, my_jobs, LZ, skip, adversarial, seed, str(e)))
+        for lens in MIXED:
+            for skip in (0.0, 0.3):
+                for adversarial in (False, True):
+                    for seed in seeds:
+                        try:
+                            simulate(0, 0, kTPS, nw, seed, ordered_reads=ordered_reads, skip_prob=skip, adversarial=adversarial,
+                                     lens=lens)
+                        except Hazard as e:
+                            bad.append((kTPS, nw, len(lens), -1, skip, adversarial, seed, f"lens {lens}: {e}"))
     if verbose:
         for b in bad[:12]:
             print("HAZARD kTPS=%d waves=%d jobs=%d LZ=%d skip=%.1f adversarial=%s seed=%d: %s" % b)
